@@ -12,6 +12,11 @@ head over all 60,000 pairs per complex -- with the reference's six-term loss (po
 + distill, main_fabind.py:398-417), over one synthetic batch of --batch complexes per GPU resident in HBM, a fresh batch object per
 step.  `--mode fwdbwd` / `fwd`: the layer stack alone (rounds 1-5's headline, now the `stack_fwdbwd` sub-object).  Prints ONE JSON line
 on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--full adds everything else to the same line: the roofline of the dominant kernel family (live HIP events), the neighbouring
+configurations (sub-objects), the CPU baseline and the north-star targets.  --dump-outputs DIR writes what the timed path computed
+in its last step (outputs, loss, parameter gradients) as DIR/<name>.npy; the inputs are seeded, identical from run to run.
 """
 import argparse
 import json
@@ -313,6 +318,52 @@ def north_star_targets(value, world, fwd_value=None, stack_value=None):
     }
 
 
+# names of the forward's return tuple (the reference's: FABind 11-tuple, FABind+ 13-tuple), for --dump-outputs
+MODEL_OUT_NAMES = ("compound_coords_pred", "compound_batch", "y_pred", "y_pred_by_coords", "pocket_cls_pred", "pocket_cls",
+                   "protein_out_mask_whole", "protein_coords_batched_whole", "pred_pocket_center", "dis_map", "keepNode_less_5",
+                   "pocket_radius_pred", "pocket_center_bias")
+DUMP_BUDGET_BYTES = 60 * 2 ** 20        # --dump-outputs: every array together stays under 64 MB
+
+
+def arrays_of(prefix, obj, names=()):
+    """(name, tensor) of every tensor or number in a (nested) tuple / list / dict of step outputs; `names` labels a tuple's items."""
+    if torch.is_tensor(obj):
+        yield prefix, obj
+    elif isinstance(obj, (bool, int, float)):
+        yield prefix, torch.tensor(float(obj), dtype=torch.float64)
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            yield from arrays_of("%s.%s" % (prefix, k), v)
+    elif isinstance(obj, (tuple, list)):
+        for i, v in enumerate(obj):
+            yield from arrays_of("%s.%s" % (prefix, names[i] if i < len(names) else i), v)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float64 for float64 and integer / bool arrays, float32 otherwise.  All together
+    stay under DUMP_BUDGET_BYTES: the smaller arrays are written whole, each larger one as a fixed, seeded sample of its flattened
+    elements (randperm(numel) with seed 0, ascending: the same indices on every run of the same shape)."""
+    import re
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = []
+    for name, t in arrays:
+        t = t.detach()
+        t = t.float() if (t.is_floating_point() and t.dtype != torch.float64) else t.to(torch.float64)
+        host.append((re.sub(r"[^A-Za-z0-9_.-]", "_", name), t.cpu()))
+    budget, left = DUMP_BUDGET_BYTES, len(host)
+    for name, t in sorted(host, key=lambda nt: (nt[1].numel() * nt[1].element_size(), nt[0])):
+        take = min(t.numel(), budget // left // t.element_size())
+        if take < t.numel():
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:take].sort().values
+            t = t.reshape(-1)[idx]
+        arr = t.numpy()
+        np.save(os.path.join(path, name + ".npy"), arr)
+        budget -= arr.nbytes
+        left -= 1
+    return len(host)
+
+
 def self_launch(n):
     """--gpus N with no launcher: spawn the N ranks as a child process group (one process per GPU over RCCL) BEFORE anything in
     this process initialises the GPU; relay the child's output and exit code.  (Never re-exec a GPU-initialised process.)"""
@@ -361,12 +412,19 @@ def main():
                     help="--mode model: unbounded pocket radius -- the complex model and the heads see the whole 1500 / 40 graph (BASELINE "
                          "configs[2] read literally; the `config3_whole_graph` sub-object of the default line)")
     ap.add_argument("--train-mode", action="store_true", help="fwdbwd / model: model.train() (dropout p = 0.1 at the reference's sites)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline of the dominant kernel family (live HIP events in the last warm-up step and "
+                         "the timed region), the neighbouring configurations as sub-objects (default mode, N=1), the CPU baseline and the "
+                         "north-star targets, all in the same JSON line.  Off: the plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (outputs, loss terms, parameter "
+                         "gradients; rank 0) as DIR/<name>.npy, float32 / float64, under 64 MB in all (larger arrays as a fixed seeded sample)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-full", action="store_true",
                     help="run ONLY SURVEY 8(d)'s CPU-baseline protocol (oracle, B=2, >=3 warm-ups + 5 timed runs, 32 threads / torch default / 1 "
                          "thread, stack pass and 8-iteration forward) on the host and print its JSON; no GPU work (tens of minutes)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default fwdbwd mode at N=1 also times, inside the same JSON line, the same step in fp32 (the mode that "
+                    help="with --full, the default mode at N=1 also times, inside the same JSON line, the same step in fp32 (the mode that "
                          "meets the 1e-4 A gate), in train mode (dropout on), at n_iter=8, forward-only, and the full IaBNet with "
                          "the six-term loss; this flag skips those sub-objects")
     a = ap.parse_args()
@@ -410,6 +468,8 @@ def main():
     # training script can make; FABIND_BENCH_ST_BACKWARD=0 restores torch's default for A/B runs.
     if os.environ.get("FABIND_BENCH_ST_BACKWARD", "1") == "1":
         torch.autograd.set_multithreading_enabled(False)
+    # --dump-outputs: the LAST timed step keeps what it computed here (timed() sets "last" just before it); None: nothing is kept
+    capture = {"last": False} if (a.dump_outputs and rank == 0) else None
 
     class _Log:
         def log_message(self, m):
@@ -453,10 +513,14 @@ def main():
                     data = hb.clone()
                     data.ligand_radius, data.num_atoms, data.isomorphisms = radius, num_atoms, isos
                     out = model(data, train=True)
-                    loss, _ = plus_loss(out, data)
+                    loss, terms = plus_loss(out, data)
                     loss.backward()
                     if reducer is not None:
                         reducer.finish()
+                    if capture is not None and capture["last"]:
+                        capture.update(outputs=out, loss=loss, loss_terms=terms)
+                if capture is not None:
+                    capture["named_params"] = list(model.named_parameters())
                 return step, a.batch, params
             torch.manual_seed(0)
             model = get_model_plus(margs, _Log()).to(dev)
@@ -467,8 +531,13 @@ def main():
             hb = synthetic.make_hetero_batch([(n_prot, a.n_lig)] * a.batch, seed=rank).to(dev)
 
             def step():
+                kept = [] if (capture is not None and capture["last"]) else None
                 for _ in range(a.poses):
-                    model.inference(hb.clone())
+                    res = model.inference(hb.clone())
+                    if kept is not None:
+                        kept.append(res)
+                if kept is not None:
+                    capture.update(outputs=kept)
             return step, a.batch, []
         if mode == "model":
             from fabind_amd import synthetic
@@ -518,12 +587,16 @@ def main():
                             if torch.is_tensor(v_) and v_.is_cuda:
                                 v_.record_stream(cur)
                 out = model(data, stage=1, train=train_mode, plan=plan)
-                loss, _ = compute_loss(out, data)
+                loss, terms = compute_loss(out, data)
                 loss.backward()
                 if reducer is not None:
                     reducer.finish()
                 if feeder is not None:
                     pending.append(arrive())                 # the next batch arrives while this step's kernels are still queued
+                if capture is not None and capture["last"]:
+                    capture.update(outputs=out, loss=loss, loss_terms=terms)
+            if capture is not None:
+                capture["named_params"] = list(model.named_parameters())
             return step, a.batch, params
         model = build_model(a.hidden, a.layers, n_iter, dropout=0.1 if train_mode else 0.0).to(dev)
         model.train(train_mode)
@@ -584,10 +657,11 @@ def main():
                 cur.wait_event(ev)
                 for v in (X0, t["batch_id"], t["segment_id"]):
                     v.record_stream(cur)
+            loss = None
             if mode == "fwd":
                 with torch.no_grad():
-                    model(X0, t["H"], t["batch_id"], t["segment_id"], t["mask"], t["is_global"], t["compound_edge_index"],
-                          t["LAS_edge_index"], t["coord_LAS"])
+                    X, Hh = model(X0, t["H"], t["batch_id"], t["segment_id"], t["mask"], t["is_global"], t["compound_edge_index"],
+                                  t["LAS_edge_index"], t["coord_LAS"])
             else:
                 for p in params:
                     p.grad = None
@@ -599,6 +673,10 @@ def main():
                     reducer.finish()
             if feeder is not None:
                 pending.append(arrive())                     # the next batch arrives while this step's kernels are still queued
+            if capture is not None and capture["last"]:
+                capture.update(outputs={"X": X, "H": Hh}, **({} if loss is None else {"loss": loss}))
+        if capture is not None:
+            capture["named_params"] = list(model.named_parameters())
         return step, a.batch, params
 
     def sync():
@@ -672,8 +750,12 @@ def main():
         K.PROFILE_BYTES.clear()
         K.PROFILE_ALGO.clear()
         K.PROFILE_ONLY = only
+        keep_last = capture is not None and steps > 0        # --dump-outputs: only the last timed step keeps its outputs
         t0 = time.time()
-        for _ in range(steps):
+        for _ in range(steps - 1 if keep_last else steps):
+            step()
+        if keep_last:
+            capture["last"] = True
             step()
         sync()
         dt = time.time() - t0
@@ -724,7 +806,17 @@ def main():
         return out_
 
     step, per_rank, _ = make_step(a.mode, a.n_iter, train_mode=a.train_mode, whole_pocket=a.whole_pocket)
-    dt, prof = timed(step, a.warmup, a.steps, os.environ.get("FABIND_BENCH_NO_PROFILE", "0") != "1")   # (=1: no per-launch events, A/B of their cost)
+    # per-launch events (the roofline; FABIND_BENCH_DUMP_PROFILE's listing) only with --full; FABIND_BENCH_NO_PROFILE=1: none even then (A/B of their cost)
+    want_profile = (a.full or bool(os.environ.get("FABIND_BENCH_DUMP_PROFILE"))) and os.environ.get("FABIND_BENCH_NO_PROFILE", "0") != "1"
+    dt, prof = timed(step, a.warmup, a.steps, want_profile)
+    if capture is not None:
+        out_names = MODEL_OUT_NAMES if a.mode in ("model", "plus_train") else ()
+        arrays = list(arrays_of("out", capture.get("outputs"), out_names))
+        arrays += list(arrays_of("loss", capture.get("loss"))) + list(arrays_of("loss_terms", capture.get("loss_terms")))
+        arrays += [("grad." + n_, p_.grad) for n_, p_ in capture.get("named_params", []) if p_.grad is not None]
+        n_dumped = dump_outputs(a.dump_outputs, arrays)
+        print("bench.py: %d arrays of the last timed step written to %s" % (n_dumped, a.dump_outputs), file=sys.stderr, flush=True)
+        capture = None
     poses = a.poses if a.mode == "plus_sampling" else 1
     value = per_rank * world * a.steps / dt * poses
     out = None
@@ -815,7 +907,7 @@ def main():
                     break
 
     # ---- the same JSON line also says what the neighbouring configurations cost (N=1, default workload only)
-    if (a.mode == "fwdbwd" or headline_config3) and world == 1 and not a.no_extras:
+    if a.full and (a.mode == "fwdbwd" or headline_config3) and world == 1 and not a.no_extras:
         extras = {}
         del step
         torch.cuda.empty_cache()
@@ -927,11 +1019,11 @@ def main():
         return
     # reported baseline: rank 0 at N=1 only, and only for the modes whose workload the stack oracle restates (the full-model and
     # FABind+ sampling modes would otherwise carry a baseline of a different workload)
-    if not a.no_cpu_baseline and world == 1 and a.mode in ("fwd", "fwdbwd"):
+    if a.full and not a.no_cpu_baseline and world == 1 and a.mode in ("fwd", "fwdbwd"):
         out["cpu_baseline"] = cpu_baseline(a.hidden, a.layers, a.n_iter, a.n_prot, a.n_lig, backward=(a.mode == "fwdbwd"))
-    if not a.no_cpu_baseline and world == 1 and headline_config3:
+    if a.full and not a.no_cpu_baseline and world == 1 and headline_config3:
         out["cpu_baseline"] = cpu_baseline_config3(a.hidden, a.layers, a.n_iter, a.n_prot, a.n_lig)
-    if headline_config3:
+    if a.full and headline_config3:
         out["north_star_targets"] = north_star_targets(out["value"], world, out.get("fwd", {}).get("value"), out.get("stack_fwdbwd", {}).get("value"))
     print(json.dumps(out))
 

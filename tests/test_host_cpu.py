@@ -433,3 +433,29 @@ def test_bench_reports_rooflines_by_the_survey_classification():
     # no time measured: zeros, not a division error; the split-bf16 mode is priced at a third of the bf16 peak
     r = bench.price_against_rooflines(1e12, 1e9, 0.0, "bf16x3", "mfma")
     assert r["achieved"] == 0.0 and r["other_roofline"]["achieved"] == 0.0 and r["peak"] == 2500.0 / 3.0
+
+
+def test_bench_dump_outputs_budget_and_sampling(tmp_path):
+    """bench.py --dump-outputs: every tensor / number of the step's outputs becomes one <name>.npy, float32 (float64 for float64 and integer
+    arrays); together they stay under 64 MB, the small arrays whole and the large ones as the same seeded sample on every call."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(4096, 4096, generator=g)                          # 64 MB alone: must be sampled
+    out = (big, torch.arange(7), {"w": torch.randn(3, 5, generator=g, dtype=torch.float64)}, 0)
+    arrays = list(bench.arrays_of("out", out, ("big", "idx"))) + [("grad.lin.weight", torch.ones(2, 2, dtype=torch.bfloat16))]
+    assert [n for n, _ in arrays] == ["out.big", "out.idx", "out.2.w", "out.3", "grad.lin.weight"]
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        assert bench.dump_outputs(str(d), arrays) == 5
+    files = sorted(os.listdir(dirs[0]))
+    assert files == sorted(os.listdir(dirs[1])) == sorted(n + ".npy" for n, _ in arrays)
+    assert sum(os.path.getsize(dirs[0] / f) for f in files) <= 64 * 2 ** 20
+    ld = {f[:-4]: np.load(dirs[0] / f) for f in files}
+    assert ld["out.idx"].dtype == np.float64 and (ld["out.idx"] == np.arange(7)).all()
+    assert ld["out.2.w"].dtype == np.float64 and ld["out.3"].shape == () and float(ld["out.3"]) == 0.0
+    assert ld["grad.lin.weight"].dtype == np.float32 and (ld["grad.lin.weight"] == 1).all()
+    s = ld["out.big"]
+    assert s.dtype == np.float32 and s.ndim == 1 and 2 ** 20 < s.size < big.numel()
+    assert np.isin(s[::1009], big.numpy().reshape(-1)).all()               # a sample of the tensor's own elements
+    for f in files:
+        assert (np.load(dirs[1] / f) == ld[f[:-4]]).all()                   # the same sample on every call

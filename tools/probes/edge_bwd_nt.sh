@@ -18,5 +18,5 @@ done
 cd $GRAFT_REPO_ROOT
 cat $O/edge_bwd_nt_pmc.txt
 for r in 1 2 3; do for m in 0 32; do
-  FABIND_EDGE_BWD3_EXP=$m python bench.py --no-cpu-baseline --no-extras --steps 10 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print('HEADLINE round $r mask $m', round(d['value'],1), round(d['ms_per_step'],2), round(d['roofline']['avg_us'],1))"
+  FABIND_EDGE_BWD3_EXP=$m python bench.py --full --no-cpu-baseline --no-extras --steps 10 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print('HEADLINE round $r mask $m', round(d['value'],1), round(d['ms_per_step'],2), round(d['roofline']['avg_us'],1))"
 done; done | tee $O/edge_bwd_nt_headline.txt

@@ -31,6 +31,6 @@ r = json.loads(buf.getvalue().strip().splitlines()[-1])
 print("FABIND_DEFER_DX=%s: %.1f complexes/s, peak allocated %.2f GB, peak reserved %.2f GB" % (os.environ["FABIND_DEFER_DX"], r["value"], torch.cuda.max_memory_allocated() / 1e9, torch.cuda.max_memory_reserved() / 1e9))
 PY
 done
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 rm -rf $O/prof $O/profs $O/profp $O/profm $O/pmc_f $O/pmc_w $O/pmc_u
 ls $O; head -12 $O/pmc_util.txt; cat $O/defer_dx_memory.txt

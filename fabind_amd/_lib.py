@@ -90,6 +90,8 @@ SIGNATURES = {
     "fabind_edge_lnfold_bwd": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _i, _vp],
     "fabind_inter_coord_fold": [_vp, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _vp, _f, ctypes.c_uint, _vp],
     "fabind_post_optimize": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "fabind_sym_automorphisms": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fabind_sym_score": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_multi_copy": [_vp, _i, _i, _vp],
     "fabind_zero_empty_rows": [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp],
     "fabind_split_sum": [_vp, _i, ctypes.c_long, _vp, _i, ctypes.c_long, _vp, _vp],

@@ -67,6 +67,7 @@ const char* fabind_last_error(void);
  *     fabind_pocket_center_fwd / _bwd (the Gumbel-softmax pocket centre, one launch each way); fabind_gemm_tn_set_exp ignores bit 2;
  *     fabind_pair_dist_fwd / _bwd, fabind_block_hadamard_bwd (+ fabind_pair_block_tile / _chunk): the distance head's pair operations on block descriptors;
  *     FabindGemmArgs.c2_bf16; fabind_node_chain_x3_fwd (node MLP / Transition as one split-precision kernel).
+ *     Backward-compatible additions under 18: fabind_sym_automorphisms / fabind_sym_score (ligand automorphisms, symmetry-corrected RMSD).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 18
 int fabind_abi_version(void);
@@ -384,6 +385,31 @@ int fabind_pair_update_fused(const FabindPairUpdateArgs* args, int H, hipStream_
 int fabind_post_optimize(const float* x0, const float* ref, const int* atom_off, const int* nbr_ptr, const int* nbr_idx,
                          int n_ligands, int max_atoms, int all_pairs, int steps, float lr, float* x_out, float* loss_out,
                          float* rmsd_out, hipStream_t stream);
+
+/* Ligand automorphisms (FABind_plus/fabind/utils/isomorphism.py:23-72: graph-tool subgraph_isomorphism(G, G, vertex_label=atomGetnum,
+ * subgraph=False), run per molecule offline by tools/inject_isomorphism_to_data.py) for a BATCH of ligands, one wave per ligand.
+ * labels: int32 [sum atoms]; nbr_ptr int32 [sum atoms + 1] / nbr_idx int32 (GLOBAL atom ids): symmetrised bond lists (every bond
+ * (i,j) listed under i and under j; entries outside the ligand and self-loops are ignored); atom_off int32 [n_ligands + 1].
+ * An automorphism a (int32 [n], a permutation) has label[a[i]] == label[i] and (i,j) bonded <=> (a[i],a[j]) bonded.
+ * Count mode (scratch = flat = NULL): count[b] = number of automorphisms, stopping at cap + 1.  Write mode: flat_off int32
+ * [n_ligands + 1] (element offsets; slot b holds min(count, cap) * n_b entries as count mode reported them), scratch / flat
+ * int32 [flat_off[n_ligands]]; flat receives the automorphisms of each ligand in ascending lexicographic order (identity first),
+ * count[b] = how many.  The identity is always kept; a truncated set is the identity plus the first cap - 1 others in search order.
+ * status[b]: 0 ok, 1 more than cap automorphisms, 2 max_steps candidate assignments exhausted, 3 n_b > 256 (identity only).
+ * Deterministic: integer arithmetic only. */
+int fabind_sym_automorphisms(const int* labels, const int* nbr_ptr, const int* nbr_idx, const int* atom_off, int n_ligands, int cap,
+                             int max_steps, const int* flat_off, int* scratch, int* flat, int* count, int* status, hipStream_t stream);
+/* Minimum over a ligand's automorphisms (FABind_plus/fabind/utils/get_sym_rmsd.py:5-18 -- spyrmsd symmrmsd without centring or
+ * superposition, per complex on the host in utils/training.py:273-286; utils/permutation_loss.py:4-33 -- the per-ligand argmin of
+ * the mean Smooth-L1) for n_pose poses at once, one work-group per (ligand, pose):
+ *   rmsd_k = sqrt(mean_i |pred[s, off_b + a_k[i]] - ref[off_b + i]|^2),  sl1_k = mean over the 3 n_b elements of SmoothL1 (beta 1).
+ * pred fp32 [n_pose, n_atoms, 3], ref fp32 [n_atoms, 3]; flat / flat_off as written by fabind_sym_automorphisms; auto_cnt[b] =
+ * automorphisms to use (0 = the identity alone: plain RMSD).  min_rmsd / min_sl1 fp32, arg_rmsd / arg_sl1 int32 [n_pose, n_ligands]:
+ * the minimum and the FIRST k reaching it.  best_idx (optional, int32 [n_atoms]): off_b + a_k[i] for the Smooth-L1 argmin of pose 0
+ * (the new_idx of the permutation-invariant loss).  Fixed summation order, no atomics: bit-reproducible.  max_atoms <= 2048. */
+int fabind_sym_score(const float* pred, int n_pose, int n_atoms, const float* ref, const int* atom_off, const int* flat_off,
+                     const int* auto_cnt, const int* flat, int n_ligands, int max_atoms, float* min_rmsd, int* arg_rmsd, float* min_sl1,
+                     int* arg_sl1, int* best_idx, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross attention (RowAttentionBlock / Attention._attention, models/cross_att.py:118-134,

@@ -10,7 +10,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FABIND_LIB") or os.path.join(_HERE, "libfabind_hip.so")      # FABIND_LIB: an A/B build (tools/probes)
 
-ABI_VERSION = 18         # FABIND_ABI_VERSION of include/fabind_hip.h this binding mirrors
+ABI_VERSION = 19         # FABIND_ABI_VERSION of include/fabind_hip.h this binding mirrors
 DT_F32, DT_BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_SIGMOID, ACT_STORED_DERIV = 0, 1, 2, 3, 4
 
@@ -115,7 +115,7 @@ SIGNATURES = {
                                    _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "fabind_layernorm_rows_bwd": [_vp, _i, _i, _vp, _vp, _i, _i, _f, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp],
     "fabind_edge_concat": [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp],
-    "fabind_las_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp],
+    "fabind_las_step": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp],
     "fabind_select_rows": [_vp, _vp, _vp, _i, _i, _vp, _vp],
     "fabind_add": [_vp, _vp, _vp, _l, _vp],
     "fabind_mul_dact": [_vp, _i, _vp, _i, _i, _vp, _i, _l, _f, _vp],

@@ -387,7 +387,7 @@ extern "C" int fabind_inter_attn_fwd(const float* qkv, int ldqkv, const float* c
 __global__ __launch_bounds__(256) FB_NO_PACKED_F32 void las_step_kernel(const float* __restrict__ x, const float* __restrict__ x0,
                                                        const int* las_i, const int* las_j, const int* las_off,
                                                        const int* node_off, const int* c_cnt, float step, float clampv,
-                                                       float* x_out, int nb_copy) {
+                                                       float* x_out, unsigned char* pass_mask, int nb_copy) {
     const int b = blockIdx.y;
     const int off = node_off[b], n = node_off[b + 1] - off, C = c_cnt[b];
     if ((int)blockIdx.x < nb_copy) {
@@ -397,6 +397,7 @@ __global__ __launch_bounds__(256) FB_NO_PACKED_F32 void las_step_kernel(const fl
         x_out[(size_t)gu * 3] = x[(size_t)gu * 3];
         x_out[(size_t)gu * 3 + 1] = x[(size_t)gu * 3 + 1];
         x_out[(size_t)gu * 3 + 2] = x[(size_t)gu * 3 + 2];
+        if (pass_mask) pass_mask[gu] = 0;               // not moved by the step: nothing flows through it
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -419,19 +420,25 @@ __global__ __launch_bounds__(256) FB_NO_PACKED_F32 void las_step_kernel(const fl
     }
     fx = wave_sum(fx); fy = wave_sum(fy); fz = wave_sum(fz);
     if (lane == 0) {
-        x_out[(size_t)gu * 3] = gx + fminf(fmaxf(fx * step, -clampv), clampv);
-        x_out[(size_t)gu * 3 + 1] = gy + fminf(fmaxf(fy * step, -clampv), clampv);
-        x_out[(size_t)gu * 3 + 2] = gz + fminf(fmaxf(fz * step, -clampv), clampv);
+        const float tx = fx * step, ty = fy * step, tz = fz * step;
+        x_out[(size_t)gu * 3] = gx + fminf(fmaxf(tx, -clampv), clampv);
+        x_out[(size_t)gu * 3 + 1] = gy + fminf(fmaxf(ty, -clampv), clampv);
+        x_out[(size_t)gu * 3 + 2] = gz + fminf(fmaxf(tz, -clampv), clampv);
+        // bit k: component k went through the clamp unchanged.  The adjoint reads this decision instead of reconstructing it from
+        // x_out - x: x_out = fl(x + clampv) does not give clampv back, and a clamped component then let its gradient through
+        // (tests/test_gpu_coord_path.py: the clamp-active cases)
+        if (pass_mask)
+            pass_mask[gu] = (unsigned char)((fabsf(tx) <= clampv ? 1 : 0) | (fabsf(ty) <= clampv ? 2 : 0) | (fabsf(tz) <= clampv ? 4 : 0));
     }
 }
 
 extern "C" int fabind_las_step(const float* x, const float* x0, const int* las_i, const int* las_j, const int* las_off,
                                const int* node_off, const int* c_cnt, int B, int max_n, float step, float clampv,
-                               float* x_out, hipStream_t stream) {
+                               float* x_out, unsigned char* pass_mask, hipStream_t stream) {
     if (B <= 0) return 0;
     const int nb_copy = (max_n + 255) / 256;
     hipLaunchKernelGGL(las_step_kernel, dim3(nb_copy + (max_n + 3) / 4, B), dim3(256), 0, stream, x, x0, las_i, las_j, las_off,
-                       node_off, c_cnt, step, clampv, x_out, nb_copy);
+                       node_off, c_cnt, step, clampv, x_out, pass_mask, nb_copy);
     FB_CHECK_LAUNCH();
     return 0;
 }

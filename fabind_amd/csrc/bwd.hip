@@ -255,7 +255,8 @@ extern "C" int fabind_rowdot_bwd(const void* z, int z_dt, const float* dpart, in
 // ------------------------------------------------------------------------------------------------
 // adjoint of edge_geom:  d=x[r]-x[c], rho=|d|^2, rhohat=rho/sqrt(sum_b rho^2)
 //   drho_e = drhohat_e/nrm - T_b rho_e / nrm^3,  T_b = sum_e drhohat_e rho_e;   g_e = dd_e + 2 drho_e d_e
-//   dx[r] += g_e, dx[c] -= g_e   (float atomics on [N,3]: order-insensitive to rounding only)
+//   dx[n] = sum_{e: row(e) = n} g_e - sum_{e: col(e) = n} g_e   (no atomics: g_e goes to a scratch buffer and one wave per node
+//   adds its row segment and its by-column group in a fixed order, so a repeat is bit-identical -- tests/test_gpu_coord_path.py)
 // ------------------------------------------------------------------------------------------------
 // pass 1: T_b per complex (one 1024-thread work-group per complex, contiguous edge range)
 __global__ __launch_bounds__(1024) void edge_geom_bwd_t_kernel(const float* __restrict__ rho, const float* __restrict__ drhohat,
@@ -1375,11 +1376,13 @@ extern "C" int fabind_inter_attn_bwd(const float* qkv, int ldqkv, const float* c
 
 // ------------------------------------------------------------------------------------------------
 // LAS step backward: x_out_j = x_j + clamp(step F_j), F_j = sum_{(i,j)} 4(|d|^2 - |d0|^2) d, d = x_i - x_j
+// pass_mask [N] (written by the forward, fabind_las_step): bit k of atom j set = component k of step F_j was inside the clamp; the entries
+// of nodes the forward does not move are 0.
 // ------------------------------------------------------------------------------------------------
 // (one wave per ligand atom, lanes over the complex's LAS edges, fixed-order wave sums; other nodes: a copy, one thread each -- the
 //  thread-per-atom form walked all 154 edges serially: 76 us per call at 2,560 atoms)
 __global__ __launch_bounds__(256) FB_NO_PACKED_F32 void las_step_bwd_kernel(const float* __restrict__ x, const float* __restrict__ x0,
-                                                           const float* __restrict__ xo, const int* las_i,
+                                                           const unsigned char* __restrict__ pass_mask, const int* las_i,
                                                            const int* las_j, const int* las_off, const int* node_off,
                                                            const int* c_cnt, float step, float clampv,
                                                            const float* __restrict__ dout, float* dx, int nb_copy) {
@@ -1400,13 +1403,11 @@ __global__ __launch_bounds__(256) FB_NO_PACKED_F32 void las_step_bwd_kernel(cons
     for (int e = las_off[b] + lane; e < las_off[b + 1]; e += 64) {
         const int i = las_i[e], j = las_j[e];
         if (i != gu && j != gu) continue;
-        // dF_j = step * dout_j * [clamp inactive]
+        // dF_j = step * dout_j * [clamp inactive], the decision being the forward's own
         float gF[3];
+        const int pm = pass_mask[j];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float delta = xo[(size_t)j * 3 + k] - x[(size_t)j * 3 + k];
-            gF[k] = fabsf(delta) < clampv ? step * dout[(size_t)j * 3 + k] : 0.f;
-        }
+        for (int k = 0; k < 3; ++k) gF[k] = ((pm >> k) & 1) ? step * dout[(size_t)j * 3 + k] : 0.f;
         const float dx_ = x[i * 3] - x[j * 3], dy_ = x[i * 3 + 1] - x[j * 3 + 1], dz_ = x[i * 3 + 2] - x[j * 3 + 2];
         const float ex = x0[i * 3] - x0[j * 3], ey = x0[i * 3 + 1] - x0[j * 3 + 1], ez = x0[i * 3 + 2] - x0[j * 3 + 2];
         const float diff = (dx_ * dx_ + dy_ * dy_ + dz_ * dz_) - (ex * ex + ey * ey + ez * ez);
@@ -1425,12 +1426,12 @@ __global__ __launch_bounds__(256) FB_NO_PACKED_F32 void las_step_bwd_kernel(cons
         dx[(size_t)gu * 3 + 2] = dout[(size_t)gu * 3 + 2] + az;
     }
 }
-extern "C" int fabind_las_step_bwd(const float* x, const float* x0, const float* xo, const int* las_i, const int* las_j,
+extern "C" int fabind_las_step_bwd(const float* x, const float* x0, const unsigned char* pass_mask, const int* las_i, const int* las_j,
                                    const int* las_off, const int* node_off, const int* c_cnt, int B, int max_n,
                                    float step, float clampv, const float* dout, float* dx, hipStream_t stream) {
     if (B <= 0) return 0;
     const int nb_copy = (max_n + 255) / 256;
-    hipLaunchKernelGGL(las_step_bwd_kernel, dim3(nb_copy + (max_n + 3) / 4, B), dim3(256), 0, stream, x, x0, xo, las_i, las_j,
+    hipLaunchKernelGGL(las_step_bwd_kernel, dim3(nb_copy + (max_n + 3) / 4, B), dim3(256), 0, stream, x, x0, pass_mask, las_i, las_j,
                        las_off, node_off, c_cnt, step, clampv, dout, dx, nb_copy);
     FB_CHECK_LAUNCH();
     return 0;

@@ -441,11 +441,14 @@ def inter_attn_fwd(qkv, cv, H, h, x, d, rhohat, rowptr, col, red_idx, bias_part,
     return h_out, x_out, alpha[:E], cvs[:E]
 
 
-def las_step(x, x0, las_i, las_j, las_off, node_off, c_cnt, B, max_n, step, clampv):
+def las_step(x, x0, las_i, las_j, las_off, node_off, c_cnt, B, max_n, step, clampv, want_mask=False):
+    """want_mask: -> (x_out, pass_mask uint8 [N]): per ligand atom, bit k set = component k of the update was inside the clamp (the
+    adjoint's clamp decision, fabind_las_step_bwd); 0 for every other node."""
     x_out = torch.empty_like(x)
+    mask = torch.empty(x.shape[0], dtype=torch.uint8, device=x.device) if want_mask else None     # (the kernel writes every entry)
     check(_lib.load().fabind_las_step(ptr(x), ptr(x0), ptr(las_i), ptr(las_j), ptr(las_off), ptr(node_off), ptr(c_cnt), B,
-                                      max_n, step, clampv, ptr(x_out), stream()), "fabind_las_step")
-    return x_out
+                                      max_n, step, clampv, ptr(x_out), ptr(mask), stream()), "fabind_las_step")
+    return (x_out, mask) if want_mask else x_out
 
 
 def select_rows(x, z, mask_u8):

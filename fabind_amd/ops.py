@@ -1724,18 +1724,18 @@ def inter_attn(qkv, cv, H, h, x, d, rhohat, g, bias_part, w_rk, w_rv, wcr, w3, c
 class _LasStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, x0, las, lay, step, clampv):
-        out = K.las_step(x, x0, las[0], las[1], las[2], lay.node_off, lay.c_cnt, lay.B, lay.max_n, step, clampv)
+        out, mask = K.las_step(x, x0, las[0], las[1], las[2], lay.node_off, lay.c_cnt, lay.B, lay.max_n, step, clampv, want_mask=True)
         ctx.las, ctx.lay, ctx.step, ctx.clampv = las, lay, step, clampv
-        ctx.save_for_backward(x, x0, out)
+        ctx.save_for_backward(x, x0, mask)          # (mask: the forward's own clamp decisions, one byte per node)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        x, x0, out = ctx.saved_tensors
+        x, x0, mask = ctx.saved_tensors
         las, lay = ctx.las, ctx.lay
         dout = dout.contiguous()
         dx = torch.empty_like(x)
-        check(load().fabind_las_step_bwd(ptr(x), ptr(x0), ptr(out), ptr(las[0]), ptr(las[1]), ptr(las[2]),
+        check(load().fabind_las_step_bwd(ptr(x), ptr(x0), ptr(mask), ptr(las[0]), ptr(las[1]), ptr(las[2]),
                                          ptr(lay.node_off), ptr(lay.c_cnt), lay.B, lay.max_n, ctx.step, ctx.clampv,
                                          ptr(dout), ptr(dx), stream()), "fabind_las_step_bwd")
         return dx, None, None, None, None, None

@@ -68,8 +68,10 @@ const char* fabind_last_error(void);
  *     fabind_pair_dist_fwd / _bwd, fabind_block_hadamard_bwd (+ fabind_pair_block_tile / _chunk): the distance head's pair operations on block descriptors;
  *     FabindGemmArgs.c2_bf16; fabind_node_chain_x3_fwd (node MLP / Transition as one split-precision kernel).
  *     Backward-compatible additions under 18: fabind_sym_automorphisms / fabind_sym_score (ligand automorphisms, symmetry-corrected RMSD).
+ * 19 = fabind_las_step writes a per-node clamp mask (new argument pass_mask), fabind_las_step_bwd takes it in place of x_out: the adjoint's
+ *     clamp decision is the forward's own (it used to be inferred from x_out - x, which fp32 rounding falsifies).
  * A binding must refuse a library whose version differs from the header it was written against. */
-#define FABIND_ABI_VERSION 18
+#define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
 /* sizeof() of an argument struct as this library was compiled: which = 0 FabindGemmArgs, 1 FabindEdgeBwdArgs,
  * 2 FabindPairUpdateArgs, 3 FabindTnJob (-1 for an unknown index).  Lets a foreign-language mirror of the struct verify its layout. */
@@ -527,10 +529,12 @@ int fabind_inter_attn_fwd_rows(const float* qkv, int ldqkv, const float* cv, int
                                const int* order, int n_heavy, int n_act, hipStream_t stream);
 
 /* LAS geometry step (models/egnn.py:433-449): x_out = x + clamp(step * sum_{(i,j): j=node} 4(|xi-xj|^2-|x0i-x0j|^2)(xi-xj)).
- * las_off[B+1]: per-complex ranges of the (complex-contiguous) LAS edge list. */
+ * las_off[B+1]: per-complex ranges of the (complex-contiguous) LAS edge list.
+ * pass_mask [N] (optional, NULL in forward-only passes): per moved atom, bit k set = component k of the update was inside the clamp
+ * (what fabind_las_step_bwd reads; every node's entry is written, 0 for the nodes that are not ligand atoms). */
 int fabind_las_step(const float* x, const float* x0, const int* las_i, const int* las_j, const int* las_off,
                     const int* node_off, const int* c_cnt, int B, int max_n, float step, float clampv, float* x_out,
-                    hipStream_t stream);
+                    unsigned char* pass_mask, hipStream_t stream);
 
 /* Pocket centre (models/model.py:146-158): per complex b over its L (padded) residues
  *   s = sigmoid(logit); p = clamp([1 - s, s], 1e-6, 1 - 1e-6); y = softmax((log p + noise) / tau) over the two classes
@@ -779,7 +783,7 @@ int fabind_inter_attn_bwd_rows(const float* qkv, int ldqkv, const float* cv, int
                                const float* cvs, float clampv, int n_rows, const float* dh_out, const float* dx_out,
                                float* dqkv, float* dcv, float* dd, float* drh, float* dbias_red, float* dlogit, float* dcp,
                                float* wpart, int nblk, const int* order, int n_heavy, int n_act, hipStream_t stream);
-int fabind_las_step_bwd(const float* x, const float* x0, const float* xo, const int* las_i, const int* las_j,
+int fabind_las_step_bwd(const float* x, const float* x0, const unsigned char* pass_mask, const int* las_i, const int* las_j,
                         const int* las_off, const int* node_off, const int* c_cnt, int B, int max_n, float step,
                         float clampv, const float* dout, float* dx, hipStream_t stream);
 int fabind_pair_bias_bwd(const float* dout, int NO, const float* ab, int ld, int H, const float* w, const int* desc_p,

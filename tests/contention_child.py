@@ -100,9 +100,9 @@ def main():
         K.tn_flush()
         bad["multi"] += cmp("multi", outs)
         for rep in range(40):                                # LAS step and its adjoint: 40 launches per pass
-            out = K.las_step(*las)
+            out, mask = K.las_step(*las, want_mask=True)
             dx = torch.empty_like(x)
-            K.check(lib.fabind_las_step_bwd(K.ptr(x), K.ptr(x0), K.ptr(out), K.ptr(las_i), K.ptr(las_j), K.ptr(las_off), K.ptr(node_off),
+            K.check(lib.fabind_las_step_bwd(K.ptr(x), K.ptr(x0), K.ptr(mask), K.ptr(las_i), K.ptr(las_j), K.ptr(las_off), K.ptr(node_off),
                                             K.ptr(c_cnt), B, max_n, step, clampv, K.ptr(g_out), K.ptr(dx), K.stream()), "fabind_las_step_bwd")
             bad["las"] += cmp("las", [out])
             bad["las_bwd"] += cmp("las_bwd", [dx])

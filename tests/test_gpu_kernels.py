@@ -1471,8 +1471,8 @@ def test_layout_ranges_is_a_lower_bound_per_complex():
 @pytest.mark.parametrize("H", [64, 256, 512])
 def test_inter_attn_rows_dealt_by_degree_match_one_wave_per_row(H, monkeypatch):
     """csrc/inter_attn_rows.hip (round 5): the inter-edge attention (egnn.py:186-252) with heavy rows split over four waves + log-sum-exp
-    combine, light rows one wave each, empty rows pass-through -- against the one-wave-per-row kernels (attn.hip / bwd.hip, themselves
-    pinned to the reference by the stack tests) on the same operands: forward outputs, every gradient of ops.inter_attn, bit-identical
+    combine, light rows one wave each, empty rows pass-through -- against the one-wave-per-row kernels (attn.hip / bwd.hip; both forms are
+    pinned, each on its own, to a float64 restatement by tests/test_gpu_coord_path.py, and to the reference by the stack tests) on the same operands: forward outputs, every gradient of ops.inter_attn, bit-identical
     repeats.  A compact complex (ligand atoms with > 64 edges: several 64-edge batches per quarter) next to an ordinary one and a third
     without any inter edge."""
     from fabind_amd import engine, kernels as K, ops, synthetic

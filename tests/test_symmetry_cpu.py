@@ -106,7 +106,7 @@ def test_symmetry_kernels_in_the_library():
     lib = _lib.load()
     for nm in ("fabind_sym_automorphisms", "fabind_sym_score"):
         assert nm in _lib.SIGNATURES and hasattr(lib, nm)
-    assert lib.fabind_abi_version() == 18
+    assert lib.fabind_abi_version() == 19
     objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
     obj = os.path.join(ROOT, "fabind_amd", "csrc", "symmetry.o")
     if not (os.path.exists(objdump) and os.path.exists(obj)):

@@ -7,8 +7,10 @@ import os
 
 import torch
 
+from . import config as _cfg
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("FABIND_LIB") or os.path.join(_HERE, "libfabind_hip.so")      # FABIND_LIB: an A/B build (tools/probes)
+LIB_PATH = _cfg.knob("FABIND_LIB") or os.path.join(_HERE, "libfabind_hip.so")      # FABIND_LIB: an A/B build (tools/probes)
 
 ABI_VERSION = 19         # FABIND_ABI_VERSION of include/fabind_hip.h this binding mirrors
 DT_F32, DT_BF16 = 0, 1
@@ -196,57 +198,29 @@ def load():
             raise RuntimeError("fabind_amd: ctypes mirror %s is %d bytes, the library's struct is %d -- _lib.py and "
                                "include/fabind_hip.h disagree" % (mirror.__name__, ctypes.sizeof(mirror),
                                                                   lib.fabind_sizeof_args(which)))
-    lib.fabind_gemm_set_config.argtypes = [ctypes.c_int]
-    lib.fabind_gemm_set_config.restype = None
-    lib.fabind_gemm_set_persistent.argtypes = [ctypes.c_int]
-    lib.fabind_gemm_set_persistent.restype = None
-    lib.fabind_gemm_set_small_m.argtypes = [ctypes.c_int]
-    lib.fabind_gemm_set_small_m.restype = None
-    lib.fabind_gemm_set_x3_tile.argtypes = [ctypes.c_int]
-    lib.fabind_gemm_set_x3_tile.restype = None
-    if os.environ.get("FABIND_GEMM_SMALL_M"):
-        lib.fabind_gemm_set_small_m(int(os.environ["FABIND_GEMM_SMALL_M"]))
-    lib.fabind_gemm_tn_set_waves.argtypes = [ctypes.c_int]
-    lib.fabind_gemm_tn_set_waves.restype = None
-    lib.fabind_gemm_tn_set_exp.argtypes = [ctypes.c_int]
-    lib.fabind_gemm_tn_set_exp.restype = None
-    lib.fabind_gemm_tn_tile_n.argtypes = []
-    lib.fabind_gemm_tn_tile_n.restype = ctypes.c_int
-    lib.fabind_gcl_edge_fused_set_xcd_aware.argtypes = [ctypes.c_int]
-    lib.fabind_gcl_edge_fused_set_xcd_aware.restype = None
-    for nm in ("fabind_gcl_edge_fused_bwd3_set_exp", "fabind_gcl_edge_fused_bwd4_set_exp"):      # development knobs (void)
-        getattr(lib, nm).argtypes = [ctypes.c_int]
-        getattr(lib, nm).restype = None
-    if os.environ.get("FABIND_EDGE_BWD3_EXP"):           # development knob: experiment mask of the store-wave backward (32 = nt operand stores)
-        lib.fabind_gcl_edge_fused_bwd3_set_exp(int(os.environ["FABIND_EDGE_BWD3_EXP"]))
-    if os.environ.get("FABIND_EDGE_BWD4_EXP"):           # sensitivity mask of the saved-forward backward (results wrong: timing only)
-        lib.fabind_gcl_edge_fused_bwd4_set_exp(int(os.environ["FABIND_EDGE_BWD4_EXP"]))
-    if "FABIND_EDGE_BWD_VARIANT" in os.environ:          # development knobs for same-box A/B runs (tools/probes)
-        lib.fabind_gcl_edge_fused_bwd_set_variant.argtypes = [ctypes.c_int]
-        lib.fabind_gcl_edge_fused_bwd_set_variant(int(os.environ["FABIND_EDGE_BWD_VARIANT"]))
-    if os.environ.get("FABIND_EDGE_FWD_VARIANT"):
-        lib.fabind_gcl_edge_fused_set_variant.argtypes = [ctypes.c_int]
-        lib.fabind_gcl_edge_fused_set_variant(int(os.environ["FABIND_EDGE_FWD_VARIANT"]))
-    if os.environ.get("FABIND_TN_WAVES"):                        # development knob: work-group layout of the TN contraction
-        lib.fabind_gemm_tn_set_waves(int(os.environ["FABIND_TN_WAVES"]))
-    if "FABIND_EDGE_XCD" in os.environ:
-        lib.fabind_gcl_edge_fused_set_xcd_aware(int(os.environ["FABIND_EDGE_XCD"]))
+    for nm in ("fabind_gemm_set_config", "fabind_gemm_set_persistent", "fabind_gemm_set_small_m", "fabind_gemm_set_x3_tile", "fabind_gemm_tn_set_waves",
+               "fabind_gemm_tn_set_exp", "fabind_gcl_edge_fused_set_xcd_aware", "fabind_gcl_edge_fused_bwd3_set_exp",
+               "fabind_gcl_edge_fused_bwd4_set_exp"):               # development setters (void)
+        getattr(lib, nm).argtypes, getattr(lib, nm).restype = [ctypes.c_int], None
+    lib.fabind_gemm_tn_tile_n.argtypes, lib.fabind_gemm_tn_tile_n.restype = [], ctypes.c_int
     for name, argt in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.argtypes = argt
         fn.restype = ctypes.c_int
+    for k in _cfg.KNOBS.values():            # development knobs of the native library: set only when the variable is
+        if k.category == "native-dev" and _cfg.knob(k.name) is not None:
+            getattr(lib, k.setter)(_cfg.knob(k.name))
     _lib = lib
     return lib
 
 
-_DEBUG_SYNC = os.environ.get("FABIND_DEBUG_SYNC", "0") == "1"     # development aid: surface a device fault at its launch
+_DEBUG_SYNC = _cfg.knob("FABIND_DEBUG_SYNC")     # development aid: surface a device fault at its launch
 
 
 def check(rc, what):
     if rc != 0:
         raise RuntimeError("%s failed (rc=%d): %s" % (what, rc, load().fabind_last_error().decode()))
     if _DEBUG_SYNC:
-        import torch
         print("[fabind] " + what, flush=True)
         torch.cuda.synchronize()
 

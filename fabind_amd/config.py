@@ -1,10 +1,83 @@
-"""Process-wide numeric mode of the HIP path."""
+"""Process-wide settings of the HIP path: the one table of FABIND_* environment variables, and the numeric mode."""
 import os
+from collections import namedtuple
 
-_PRECISION = {"mode": "bf16", "x3_backward": "bf16" if (os.environ.get("FABIND_X3_WGRAD", "bf16") == "bf16" and
-                                                          os.environ.get("FABIND_X3_PAIRBIAS_BWD", "bf16") == "bf16") else "exact"}
+# Every FABIND_* environment variable the package reads.  Categories:
+#   'mode-seed'   seeds the default of a numerics mode of this module's set_* API (results change; parity asserted in the GPU suite);
+#   'ab'          switch between two implementations of the same arithmetic;
+#   'native-dev'  handed to a setter of the native library (`setter`) by _lib.load() when set;
+#   'debug'       development aids.
+# attr: the module attribute (or function) the value lands in, read once at import; tests and probes assign those attributes.
+# type: bool is on exactly for "1" -- `lenient` ones for everything but "0" --, int / str parse the value; an unset variable reads as
+# `default` (None: the native setter is not called; there an empty value counts as unset too).  exercised_by: the test or tool that drives the non-default side of an 'ab' / 'native-dev' knob;
+# one that nothing drives does not stay (tests/test_host_cpu.py).
+Knob = namedtuple("Knob", "name default type category doc exercised_by attr setter lenient", defaults=(None, None, None, False))
+
+KNOBS = {k.name: k for k in (
+    Knob("FABIND_X3_WGRAD", "bf16", str, "mode-seed", "'bf16x3': anything but bf16 seeds set_x3_backward('exact') (split weight-gradient contractions)"),
+    Knob("FABIND_X3_PAIRBIAS_BWD", "bf16", str, "mode-seed", "'bf16x3': anything but bf16 seeds set_x3_backward('exact') (fp32 pair-bias adjoint)"),
+    Knob("FABIND_SPLIT_SITES", 3, int, "mode-seed", "'bf16': default of set_split_sites(level), 0-3"),
+    Knob("FABIND_X3_EDGE", "split", str, "mode-seed", "'bf16x3': default of set_x3_edge(kind), split / bf16"),
+    Knob("FABIND_ATTN_FUSED_TRAIN", True, bool, "ab", "0: the differentiable pass reads / writes [pairs, 8] bias tensors (round 3)", "tests/test_gpu_attn_mfma.py", "ops.FUSED_ATTN_TRAIN"),
+    Knob("FABIND_EDGE_SAVE_FWD", True, bool, "ab", "0: the recompute backward (four contractions, nothing kept)", "tools/probes/edge_saved_forward_ab.sh", "ops.EDGE_SAVE_FWD", lenient=True),
+    Knob("FABIND_FUSE_DB_TN", True, bool, "ab", "bias gradients ride along with the TN weight-gradient contraction", "tools/probes/db_tn_ab.sh", "ops.FUSE_DB_TN"),
+    Knob("FABIND_INTER_ATTN_ROWS", True, bool, "ab", "0: one wave per row whatever its degree (rounds 1-4; A/B)", "tests/test_gpu_kernels.py", "kernels.INTER_ATTN_ROWS"),
+    Knob("FABIND_LAYOUT_CACHE", True, bool, "ab", "0: Layout.of rebuilds the layout on every call (A/B)", "tools/probes/layout_cache_ab.sh", "engine.LAYOUT_CACHE", lenient=True),
+    Knob("FABIND_PAIRHAD_ROWS", True, bool, "ab", "adjoint of the pair Hadamard as a row walk of the inter graph (no atomics)", "tools/probes/pairhad_ab.sh", "ops.PAIRHAD_ROWS"),
+    Knob("FABIND_PARAM_PACK", "1", str, "ab", "0: parameter views as torch ops per entry (round 1); check: verify that no parameter element "
+         "is requested twice; read at call time (param_pack())", "tests/test_gpu_param_pack.py", "config.param_pack"),
+    Knob("FABIND_PLUS_FOLD_EDGE_LN", True, bool, "ab", "0: no LayerNorm-folded edge / coordinate Linears (A/B)", "tools/probes/plus_ab_samebox.sh", "plus.engine.FOLD_EDGE_LN"),
+    Knob("FABIND_PLUS_FOLD_EDGE_LN_TRAIN", True, bool, "ab", "0: under autograd concat -> LayerNorm -> GEMM (rounds 1-4; A/B)", "tests/test_gpu_plus.py", "plus.engine.FOLD_EDGE_LN_TRAIN"),
+    Knob("FABIND_PLUS_FUSE_PAIR", True, bool, "ab", "0: the pair update of no-grad bf16 passes as separate kernels (A/B)", "tools/probes/plus_ab_samebox.sh", "plus.engine.FUSE_PAIR"),
+    Knob("FABIND_ROWS_HADAMARD_WALK", True, bool, "ab", "adjoint of rows_hadamard as a row walk (0: float atomics)", "tests/test_gpu_kernels.py", "ops.ROWS_HADAMARD_WALK"),
+    Knob("FABIND_TN_DEFER", True, bool, "ab", "0: every contraction is its own launch pair (round 3's behaviour; A/B)", "tests/test_gpu_kernels.py", "kernels.TN_DEFER"),
+    Knob("FABIND_EDGE_BWD3_EXP", None, int, "native-dev", "experiment mask of the store-wave backward (32 = nt operand stores)", "tools/probes/edge_bwd_nt.sh", "_lib.load", "fabind_gcl_edge_fused_bwd3_set_exp"),
+    Knob("FABIND_EDGE_BWD_VARIANT", None, int, "native-dev", "form of the fused edge backward, for same-box A/B runs", "tools/probes/edge_knobs_ab.sh", "_lib.load", "fabind_gcl_edge_fused_bwd_set_variant"),
+    Knob("FABIND_GEMM_SMALL_M", None, int, "native-dev", "row count below which fabind_gemm takes its small-M tile (0: never)", "tools/probes/small_m_ab.sh", "_lib.load", "fabind_gemm_set_small_m"),
+    Knob("FABIND_TN_WAVES", None, int, "native-dev", "work-group layout of the TN contraction", "tools/probes/tn_layout_ab.sh", "_lib.load", "fabind_gemm_tn_set_waves"),
+    Knob("FABIND_DEBUG_GRAPH", False, bool, "debug", "validate the inter-graph CSR on the host", attr="engine.DEBUG_GRAPH"),
+    Knob("FABIND_DEBUG_SYNC", False, bool, "debug", "synchronise after every launch: a device fault surfaces at its launch", attr="_lib._DEBUG_SYNC"),
+    Knob("FABIND_LIB", "", str, "debug", "path of the library to load instead of the built one: an A/B build (tools/probes)", attr="_lib.LIB_PATH"),
+)}
+
+
+def read(name, env):
+    """Value of variable `name` in the mapping `env`, parsed by its declared type.  An unknown name is an error."""
+    k = KNOBS[name]
+    raw = env.get(name)
+    if k.type is bool:
+        return k.default if raw is None else (raw != "0" if k.lenient else raw == "1")
+    if raw is None or (raw == "" and k.default is None):
+        return k.default
+    return k.type(raw)
+
+
+_VALUES = {name: read(name, os.environ) for name in KNOBS}        # evaluated once, at import
+
+
+def knob(name):
+    return _VALUES[name]
+
+
+def param_pack():
+    """FABIND_PARAM_PACK as of now ('1' / '0' / 'check'): the one variable read at call time (tests/test_gpu_param_pack.py changes it)."""
+    return read("FABIND_PARAM_PACK", os.environ)
+
+
+def knobs_markdown():
+    """The table of docs/KNOBS.md's A/B section (`python -m fabind_amd.config`)."""
+    show = lambda d: "unset" if d in (None, "") else "`%s`" % (int(d) if isinstance(d, bool) else d)
+    rows = ["| variable | default | file | note |", "|---|---|---|---|"]
+    for k in sorted(KNOBS.values(), key=lambda k_: k_.name):
+        if k.category != "mode-seed":
+            where = "`fabind_amd/%s.py`" % k.attr.rsplit(".", 1)[0].replace(".", "/")
+            rows.append("| `%s` | %s | %s | %s%s |" % (k.name, show(k.default), where, k.doc, " (`%s`)" % k.exercised_by if k.exercised_by else ""))
+    return "\n".join(rows)
+
+
+_PRECISION = {"mode": "bf16", "x3_backward": "bf16" if (knob("FABIND_X3_WGRAD") == "bf16" and knob("FABIND_X3_PAIRBIAS_BWD") == "bf16") else "exact"}
 MODES = ("fp32", "bf16", "bf16x3")
-_PRECISION["split_sites"] = int(os.environ.get("FABIND_SPLIT_SITES", "3"))
+_PRECISION["split_sites"] = knob("FABIND_SPLIT_SITES")
 
 
 def set_precision(mode):
@@ -59,7 +132,7 @@ def split_sites():
     return _PRECISION["split_sites"] if _PRECISION["mode"] == "bf16" else 0
 
 
-_PRECISION["x3_edge"] = os.environ.get("FABIND_X3_EDGE", "split")
+_PRECISION["x3_edge"] = knob("FABIND_X3_EDGE")
 
 
 def set_x3_edge(kind):
@@ -99,3 +172,7 @@ def get_precision():
 def fp32_storage():
     """True in the modes that keep every activation / weight in fp32 ('fp32' and 'bf16x3')."""
     return _PRECISION["mode"] != "bf16"
+
+
+if __name__ == "__main__":
+    print(knobs_markdown())

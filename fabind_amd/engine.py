@@ -18,11 +18,10 @@ touches activations runs in libfabind_hip.so.
 """
 import math
 
-import os
-
 import numpy as np
 import torch
 
+from . import config as _cfg
 from . import kernels as K
 from . import ops
 
@@ -32,6 +31,8 @@ from .param_pack import EagerPack, ParamPack
 
 
 FUSED_EDGE = True     # forward-only bf16: fused gather->GEMM->GEMM->segment-sum edge kernel
+LAYOUT_CACHE = _cfg.knob("FABIND_LAYOUT_CACHE")      # 0: Layout.of rebuilds the layout on every call (A/B)
+DEBUG_GRAPH = _cfg.knob("FABIND_DEBUG_GRAPH")        # development aid: validate the CSR on the host
 DEBUG_CAPTURE = None  # set to a dict to record per-layer outputs of the LAST egnn_forward call (tests)
 
 
@@ -58,7 +59,7 @@ class Layout:
     @classmethod
     def of(cls, batch_id, segment_id, n_pair_out=8):
         import weakref
-        if os.environ.get("FABIND_LAYOUT_CACHE", "1") == "0":       # development knob for same-box A/B runs
+        if not LAYOUT_CACHE:
             return cls(batch_id, segment_id, n_pair_out)
         for ent in cls._cache:
             if ent[0]() is batch_id and ent[2]() is segment_id and ent[1] == batch_id._version and ent[3] == segment_id._version \
@@ -192,7 +193,7 @@ class Graph:
                 x, lay.node_off, lay.c_cnt, lay.B, lay.max_n, bond_row, bond_col, bond_off, cut_intra, cut_inter, rp_ctx,
                 rp_int, E_ctx, E_int)
         self.rp_ctx, self.rp_int, self.E_ctx, self.E_int = rp_ctx, rp_int, E_ctx, E_int
-        if os.environ.get("FABIND_DEBUG_GRAPH", "0") == "1":             # development aid: validate the CSR on the host
+        if DEBUG_GRAPH:
             r, c, Nn = self.row_int.long(), self.col_int.long(), lay.N
             k1, k2 = torch.sort(r * Nn + c)[0], torch.sort(c * Nn + r)[0]
             nbad = int((k1 != k2).sum())
@@ -334,7 +335,6 @@ def att_edge_composed(m, d):
     d["wcr"] = (m.coord_mlp[0].weight @ d["w_rv"]).contiguous()
 
 
-PACK_PLAN = os.environ.get("FABIND_PACK_PLAN", "1") == "1"      # keep a model's pack requests across calls (0: rebuild them per call, A/B)
 _PLAN_CACHE = {}           # id(model) -> (key, ParamPack with its requests, request tree, weakref(model))
 
 
@@ -346,7 +346,7 @@ def _stack_requests(model):
     L = gnn.n_layers
     il = model.inter_layer
     dev = il.linear_p.weight.device
-    pk = EagerPack(dev) if os.environ.get("FABIND_PARAM_PACK", "1") == "0" else ParamPack(dev)
+    pk = EagerPack(dev) if _cfg.param_pack() == "0" else ParamPack(dev)
     P = {"H": H, "L": L}
     P["W_ab0"] = pk.cat([il.linear_p.weight, il.linear_c.weight], 0, wd, with_T=True)
     P["b_ab0"] = pk.cat([il.linear_p.bias, il.linear_c.bias])
@@ -394,9 +394,9 @@ def _build_stack_params(model):
     L = gnn.n_layers
     il = model.inter_layer
     params = last_params_of(model)
-    key = (get_precision(), os.environ.get("FABIND_PARAM_PACK", "1"), tuple((id(p_), p_.data_ptr(), p_.requires_grad) for p_ in params))
+    key = (get_precision(), _cfg.param_pack(), tuple((id(p_), p_.data_ptr(), p_.requires_grad) for p_ in params))
     ent = _PLAN_CACHE.get(id(model))
-    if ent is not None and ent[0] == key and ent[3]() is model and isinstance(ent[1], ParamPack) and PACK_PLAN:
+    if ent is not None and ent[0] == key and ent[3]() is model and isinstance(ent[1], ParamPack):
         pk, tree = ent[1], ent[2]
     else:
         import weakref
@@ -468,7 +468,7 @@ def _split_site_masters(model, P):
                 d = P["gcl"][i] if i < P["L"] else P["out_layer"]
                 d["Wn_32"] = (f32(m.node_mlp[0].weight), f32(m.node_mlp[2].weight))
             # the hi | lo fragment packs of every split-precision chain (node MLPs, both Transitions) of the model: ONE launch
-            if NODE_CHAIN and NODE_CHAIN_X3 and P["H"] in (128, 256, 512):
+            if P["H"] in (128, 256, 512):
                 chains, where = [], []
                 for i in range(P["L"] + 1):
                     d = P["gcl"][i] if i < P["L"] else P["out_layer"]
@@ -519,15 +519,12 @@ def _drop(t, pr):
     return torch.nn.functional.dropout(t, pr, True) if pr > 0.0 else t
 
 
-NODE_CHAIN = os.environ.get("FABIND_NODE_CHAIN", "1") == "1"     # forward-only bf16 passes: node MLP / Transition as one kernel (csrc/node_chain.hip)
-
-
 def _node_chain(p, key, W1, b1, W2, b2, act, kind, x1, x2, residual, want16):
-    """Linear -> act -> Linear + residual as one forward kernel with the hidden activation in LDS; None when the shapes do not fit
+    """Linear -> act -> Linear + residual as one forward kernel with the hidden activation in LDS (forward-only bf16 passes; csrc/node_chain.hip); None when the shapes do not fit
     (H in {128, 256, 512}; kind 0: W1 [H, 2H]; kind 1: W1 [2H, H]).  The fragment packs are kept in the (cached, no-grad) parameter
     pack p under `key`."""
     H = W2.shape[0]
-    if not (NODE_CHAIN and H in (128, 256, 512) and W1.dtype == torch.bfloat16 and b1 is not None and b2 is not None
+    if not (H in (128, 256, 512) and W1.dtype == torch.bfloat16 and b1 is not None and b2 is not None
             and x1.dtype == torch.bfloat16 and x1.shape[1] == H and x1.stride(1) == 1 and x1.stride(0) % 8 == 0
             and residual.dtype == torch.float32 and residual.stride(1) == 1 and residual.stride(0) % 4 == 0
             and W1.shape == ((H, 2 * H) if kind == 0 else (2 * H, H)) and W2.shape == ((H, H) if kind == 0 else (H, 2 * H))):
@@ -547,7 +544,7 @@ def _node_chain_x3(p, key, W32, b1, b2, act, kind, x1, x2, residual, want16):
     H = W32[1].shape[0]
     ok = lambda t: t is not None and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == H and t.stride(1) == 1 and t.stride(0) % 4 == 0 \
         and t.data_ptr() % 16 == 0
-    if not (NODE_CHAIN and NODE_CHAIN_X3 and H in (128, 256, 512) and b1 is not None and b2 is not None and ok(x1) and ok(residual)
+    if not (H in (128, 256, 512) and b1 is not None and b2 is not None and ok(x1) and ok(residual)
             and (kind == 1 or ok(x2)) and tuple(W32[0].shape) == ((H, 2 * H) if kind == 0 else (2 * H, H))
             and tuple(W32[1].shape) == ((H, H) if kind == 0 else (H, 2 * H))):
         return None
@@ -557,10 +554,6 @@ def _node_chain_x3(p, key, W32, b1, b2, act, kind, x1, x2, residual, want16):
             packs = p[key] = K.node_chain_x3_pack_many([(W32[0].detach(), W32[1].detach(), kind)])[0]      # (one launch)
     out, out16 = K.node_chain_x3_fwd(x1, x2 if kind == 0 else None, packs, b1.float(), b2.float(), act, kind, residual=residual, want16=want16)
     return ops._attach_b16(out, out16)
-
-
-X3_NOGRAD_CHAIN = os.environ.get("FABIND_X3_NOGRAD_CHAIN", "1") == "1"   # 0: no-grad passes of 'bf16x3' run their MLPs as two gemm_x3 launches (A/B)
-NODE_CHAIN_X3 = os.environ.get("FABIND_NODE_CHAIN_X3", "1") == "1"     # 0: the split-precision MLPs of no-grad passes as two gemm_x3 launches (A/B)
 
 
 def gcl_layer(p, h, x, lay, g, clampv, pdrop=0.0):
@@ -595,7 +588,7 @@ def gcl_layer(p, h, x, lay, g, clampv, pdrop=0.0):
             k_ = "gcl_dbg_%d" % sum(1 for q in DEBUG_CAPTURE if q.startswith("gcl_dbg_") and q.endswith(".s"))
             DEBUG_CAPTURE[k_ + ".xin"], DEBUG_CAPTURE[k_ + ".d"], DEBUG_CAPTURE[k_ + ".rhohat"] = x.detach().clone(), d.detach().clone(), rhohat.detach().clone()
             DEBUG_CAPTURE[k_ + ".agg"], DEBUG_CAPTURE[k_ + ".s"] = agg.detach().clone(), s.detach().clone()
-        if (get_precision() == "bf16x3" and X3_NOGRAD_CHAIN and pdrop == 0.0 and p["Wn1"].dtype == torch.float32
+        if (get_precision() == "bf16x3" and pdrop == 0.0 and p["Wn1"].dtype == torch.float32
                 and not ops.needs_grad(h, agg, p["Wn1"], p["Wn2"])):
             # round 6: a no-grad pass of the 'bf16x3' mode takes the same split-precision chain kernel (fp32 weights -> hi | lo packs, cached
             # with the no-grad parameter pack): no fp32 hidden layer in HBM
@@ -696,7 +689,7 @@ def cross_attention(p, h, lay, pairbias, layer, pdrop=0.0):
             t = ops.linear(hc16, p["Wt1_c"], p["bt1_c"], act_epi=K.ACT_RELU, out_dtype=od)
             hc2 = ops.linear(t, p["Wt2_c"], p["bt2_c"], residual=hc)
         hc = hc2
-    elif (get_precision() == "bf16x3" and X3_NOGRAD_CHAIN and p["Wt1_p"].dtype == torch.float32
+    elif (get_precision() == "bf16x3" and p["Wt1_p"].dtype == torch.float32
           and not ops.needs_grad(hp, hc, p["Wt1_p"], p["Wt2_p"], p["Wt1_c"], p["Wt2_c"])):
         hp2 = _node_chain_x3(p, "_ncx3_tp", (p["Wt1_p"], p["Wt2_p"]), p["bt1_p"], p["bt2_p"], K.ACT_RELU, 1, hp, None, hp, True)
         hp = hp2 if hp2 is not None else ops.mlp2(hp, p["Wt1_p"], p["bt1_p"], K.ACT_RELU, p["Wt2_p"], p["bt2_p"], residual=hp, want16=True)

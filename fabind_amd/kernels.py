@@ -1,12 +1,12 @@
 """Thin Python wrappers over the C ABI (include/fabind_hip.h): allocate outputs with torch, pass raw
 device pointers + the current HIP stream.  No math happens here."""
 import ctypes
-import os
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import config as _cfg
 from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU, ACT_STORED_DERIV, GemmArgs, check, dt_code, ptr, stream
 
 __all__ = ["gemm", "transpose_act", "colsum", "edges_count", "edges_fill", "exclusive_scan", "inter_meta",
@@ -280,7 +280,6 @@ def cross_attn_fwd(q, k, v, gpre, bias, lin_col, gate_col, desc, B, max_nq, scal
     return out, lse
 
 
-CROSS_ATTN_FUSED = os.environ.get("FABIND_ATTN_FUSED", "1") == "1"   # forward-only bf16 passes: pair bias recomputed inside the attention kernels
 CROSS_ATTN_FUSED_MAX_C = 62
 
 
@@ -344,21 +343,10 @@ def bot_ksteps(lay):
     return c
 
 
-def pair_bot_pack(b0, wcomp, H, lay):
-    """Packed bf16 operands Bo^T of ALL layers / blocks for the fused backward, one launch (include/fabind_hip.h: fabind_pair_bot_pack)."""
-    koff, kstep_b, n_ks = bot_ksteps(lay)
-    wc = wcomp.reshape(-1, 8, wcomp.shape[-1]).float().contiguous()
-    nblk = wc.shape[0]
-    per = max(n_ks, 1) * (H // 16) * 512
-    out = torch.empty((nblk, per), dtype=torch.bfloat16, device=b0.device)
-    check(_lib.load().fabind_pair_bot_pack(ptr(b0), _ld(b0), ptr(wc), H, ptr(lay.c_index), ptr(lay.desc_pf), ptr(koff), ptr(kstep_b), n_ks,
-                                           ptr(out), nblk, per, stream()), "fabind_pair_bot_pack")
-    return [out[k] for k in range(nblk)]
-
-
-def cross_attn_fused_bwd(qg, kv, a0_16, bo, boT, bconst8, lay, H, mode, scale, out, lse, dout, dqg, dkv, da0b0, acat, kcol0, colpart, kp):
+def cross_attn_fused_bwd(qg, kv, a0_16, bo, bconst8, lay, H, mode, scale, out, lse, dout, dqg, dkv, acat, kcol0, colpart, kp):
     """Fused backward of the cross attention (include/fabind_hip.h: fabind_cross_attn_fused_bwd).  dqg / dkv are written (covered rows),
-    da0b0[:, :H] is accumulated, acat[:, kcol0 : kcol0 + C * 8] receives the bf16 gradient rows, colpart (a [tiles, >= 8] view: the
+    acat[:, kcol0 : kcol0 + C * 8] receives the bf16 gradient rows (d a0 is the caller's ragged GEMM over them: the kernel's own d a0
+    contraction gets null operands boT / da0), colpart (a [tiles, >= 8] view: the
     first 8 columns of every row) the per-tile column sums of the per-pair gradients in slot order lin0, gate0, lin1, gate1, ..."""
     lib = _lib.load()
     toff, _, _ = bo_tiles(lay)
@@ -369,12 +357,12 @@ def cross_attn_fused_bwd(qg, kv, a0_16, bo, boT, bconst8, lay, H, mode, scale, o
     Dv = torch.empty((nq, 4), dtype=torch.float32, device=dev)
     part = torch.empty(max(1, int(lib.fabind_cross_attn_fused_bwd_scratch(lay.B, lay.max_P, lay.max_C, lay.sumC, mode))), dtype=torch.float32, device=dev)
     a = _lib.AttnFusedBwdArgs()
-    for name, t in (("qg", qg), ("kv", kv), ("a0", a0_16), ("bo", bo), ("boT", boT), ("toff", toff), ("koff", koff), ("bconst", bconst8),
+    for name, t in (("qg", qg), ("kv", kv), ("a0", a0_16), ("bo", bo), ("toff", toff), ("koff", koff), ("bconst", bconst8),
                     ("desc", lay.desc_pf), ("desc_p", lay.desc_p), ("out", out), ("lse", lse), ("dout", dout), ("dqg", dqg), ("dkv", dkv),
-                    ("dO", dO), ("Dv", Dv), ("da0", da0b0), ("acat", acat), ("colpart", colpart), ("part", part)):
+                    ("dO", dO), ("Dv", Dv), ("acat", acat), ("colpart", colpart), ("part", part)):
         setattr(a, name, ptr(t))
     a.ldq, a.ldkv, a.lda0, a.ldacat, a.kcol0, a.ldcolpart = _ld(qg), _ld(kv), _ld(a0_16), _ld(acat), int(kcol0), colpart.stride(0)
-    a.ldda0 = _ld(da0b0) if da0b0 is not None else 0
+    a.ldda0 = 0
     a.kp = int(kp)
     a.scale = float(scale)
     nsplit = (lay.max_P + 63) // 64
@@ -408,7 +396,7 @@ def pair_hadamard(a0, b0, a1, b1, red_p, red_c, out_dtype):
     return hd
 
 
-INTER_ATTN_ROWS = os.environ.get("FABIND_INTER_ATTN_ROWS", "1") == "1"    # 0: one wave per row whatever its degree (rounds 1-4; A/B)
+INTER_ATTN_ROWS = _cfg.knob("FABIND_INTER_ATTN_ROWS")    # 0: one wave per row whatever its degree (rounds 1-4; A/B)
 INTER_ATTN_HEAVY = 8                                                      # = IA_HEAVY of csrc/inter_attn_rows.hip
 
 
@@ -906,9 +894,9 @@ def _tn_splits(M, N, E, tn):
 # ------------------------------------------------------------------------------------------------
 # queued weight-gradient contractions (fabind_gemm_tn_multi)
 # ------------------------------------------------------------------------------------------------
-TN_DEFER = os.environ.get("FABIND_TN_DEFER", "1") == "1"          # 0: every contraction is its own launch pair (round 3's behaviour; A/B)
-TN_DEFER_JOB_BYTES = int(os.environ.get("FABIND_TN_DEFER_JOB_MB", "1024")) << 20     # operands larger than this fill the chip alone: launched at once
-TN_DEFER_QUEUE_BYTES = int(os.environ.get("FABIND_TN_DEFER_QUEUE_MB", "6144")) << 20   # operand bytes the queue may keep alive
+TN_DEFER = _cfg.knob("FABIND_TN_DEFER")          # 0: every contraction is its own launch pair (round 3's behaviour; A/B)
+TN_DEFER_JOB_BYTES = 1024 << 20     # operands larger than this fill the chip alone: launched at once
+TN_DEFER_QUEUE_BYTES = 6144 << 20   # operand bytes the queue may keep alive
 _TNQ = {"jobs": [], "bytes": 0, "armed": False, "outs": set()}
 _TNJOB = np.dtype([(n_, np.uint64) for n_ in ("Y", "X", "C_part", "out", "out_tail")] +
                   [(n_, np.int32) for n_ in ("ldy", "ldx", "M", "N", "E", "splits", "e_per", "n_tiles", "with_colsum", "out_dt", "ldo",

@@ -5,8 +5,6 @@ when a gradient is required the same kernels run inside torch.autograd.Function 
 backward passes are HIP kernels as well (fabind_amd/csrc/bwd.hip + the GEMM family)."""
 import ctypes
 
-import os
-
 import numpy as np
 import torch
 
@@ -55,7 +53,7 @@ def _transposed(x, act=K.ACT_NONE, Rp=None):
     return out
 
 
-FUSE_DB_TN = os.environ.get("FABIND_FUSE_DB_TN", "1") == "1"   # bias gradients ride along with the TN weight-gradient contraction
+FUSE_DB_TN = _cfg.knob("FABIND_FUSE_DB_TN")   # bias gradients ride along with the TN weight-gradient contraction
 
 
 def _tn_ok(dpre, x, x2):
@@ -183,8 +181,7 @@ def _mul_dact(dy, aux, act, out_dtype, scale=1.0):
     return out
 
 
-FUSE_DB = os.environ.get("FABIND_FUSE_DB", "1") == "1"
-DB_IN_TN_ROWS = int(os.environ.get("FABIND_DB_IN_TN_ROWS", "32768"))
+DB_IN_TN_ROWS = 32768
 
 
 def _db_in_tn(dy):
@@ -309,7 +306,7 @@ class _Linear(torch.autograd.Function):
         md = mm_dtype()
         db = None
         want_db = ctx.has_b and ctx.needs_input_grad[2]
-        fuse_db = FUSE_DB and want_db and dy.dim() == 2 and dy.shape[1] % 4 == 0   # bias gradient in the same pass over dy
+        fuse_db = want_db and dy.dim() == 2 and dy.shape[1] % 4 == 0   # bias gradient in the same pass over dy
         if fuse_db and ctx.needs_input_grad[1] and _db_in_tn(dy):
             fuse_db = False                                                       # ... or with the queued weight-gradient contraction
         md_op = _mul_dact_colsum if fuse_db else (lambda *a: (_mul_dact(*a), None))      # (dy, aux, act, out dtype[, scale])
@@ -535,14 +532,11 @@ class _MLP2(torch.autograd.Function):
         return dx, dx2, dW1, db1, dW2, (db2 if ni[5] else None), dres, None, None, None, None, None, None
 
 
-MLP2_CHAIN = os.environ.get("FABIND_MLP2_CHAIN", "1") == "1"       # 0: the split-precision MLPs under autograd as two gemm_x3 launches (A/B)
-
-
 def _chain_ok(x, x2, residual, W1, W2):
     H = W2.shape[0]
     ok = lambda t: t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == H and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
     kind0 = x2 is not None
-    return (MLP2_CHAIN and H in (128, 256, 512) and ok(x) and (x2 is None or ok(x2)) and (residual is None or ok(residual))
+    return (H in (128, 256, 512) and ok(x) and (x2 is None or ok(x2)) and (residual is None or ok(residual))
             and tuple(W1.shape) == ((H, 2 * H) if kind0 else (2 * H, H)) and tuple(W2.shape) == ((H, H) if kind0 else (H, 2 * H)))
 
 
@@ -793,16 +787,13 @@ def edge_tail(Mm, Wc, bc, w3, rowptr, row, n_rows, act_epi=K.ACT_SILU):
     return part, K.segment_sum(Mm, rowptr, n_rows)
 
 
-EDGE_SAVE_FWD = os.environ.get("FABIND_EDGE_SAVE_FWD", "1") != "0"          # 0: the recompute backward (four contractions, nothing kept)
-EDGE_SAVE_MIN_EDGES = int(os.environ.get("FABIND_EDGE_SAVE_MIN_EDGES", "0"))
+EDGE_SAVE_FWD = _cfg.knob("FABIND_EDGE_SAVE_FWD")          # 0: the recompute backward (four contractions, nothing kept)
 # (hidden 128 -- the pocket model of the full IaBNet on whole proteins, 1.5 M edges: forward 280 -> 434 us, backward 1,086 -> 657 us per launch with
-#  FABIND_EDGE_SAVE_MIN_H=128, but the full-model step is host-bound there: 1,234 / 1,301 / 1,351 against 1,308 / 1,313 / 1,304 complexes/s in
+#  EDGE_SAVE_MIN_H = 128, but the full-model step is host-bound there: 1,234 / 1,301 / 1,351 against 1,308 / 1,313 / 1,304 complexes/s in
 #  three interleaved pairs (profiles/r04_ab_same_box.txt) -- the default stays 256, which keeps 1.2 GB per pocket-model layer free)
-EDGE_SAVE_MIN_H = int(os.environ.get("FABIND_EDGE_SAVE_MIN_H", "256"))
-# (round 6, measured and NOT enabled: the saving form for large graphs at hidden 128 -- E >= EDGE_SAVE_BIG_EDGES edges -- reads 539 / 538 against
-#  543 / 547 complexes/s on the config-3 headline and 1,371 / 1,342 against 1,326 / 1,335 on the production-shape model step, two interleaved
-#  pairs each (profiles/r06_ab_same_box.txt): the default keeps it off)
-EDGE_SAVE_BIG_EDGES = int(os.environ.get("FABIND_EDGE_SAVE_BIG_EDGES", "2000000000"))
+EDGE_SAVE_MIN_H = 256
+# (round 6, measured and not adopted: the saving form for large graphs at hidden 128 reads 539 / 538 against 543 / 547 complexes/s on the config-3
+#  headline and 1,371 / 1,342 against 1,326 / 1,335 on the production-shape model step, two interleaved pairs each (profiles/r06_ab_same_box.txt))
 
 
 class _FusedEdge(torch.autograd.Function):
@@ -815,7 +806,7 @@ class _FusedEdge(torch.autograd.Function):
         ctx.H, ctx.g, ctx.p_drop, ctx.seed, ctx.frags = H, g, p_drop, seed, frags
         W2p, Wcp = (frags[0], frags[1]) if frags is not None else (K.pack_frag(W2), K.pack_frag(Wc))
         E = g.row_ctx.shape[0]
-        save = EDGE_SAVE_FWD and (H >= EDGE_SAVE_MIN_H or (H >= 128 and E >= EDGE_SAVE_BIG_EDGES)) and E >= max(1, EDGE_SAVE_MIN_EDGES) and AB16.dtype == torch.bfloat16
+        save = EDGE_SAVE_FWD and H >= EDGE_SAVE_MIN_H and E >= 1 and AB16.dtype == torch.bfloat16
         out = K.gcl_edge_fused(AB16, H, g.row_ctx, g.col_ctx, rhohat, w_r, W2p, b2, Wcp, bc, w3,
                                AB16.shape[0], p_drop, seed, want16=holder is not None, rowptr=g.rp_ctx, save=save)
         ctx.n_saved = 3 if save else 0
@@ -853,7 +844,7 @@ class _FusedEdgeX3(torch.autograd.Function):
     def forward(ctx, AB, rhohat, w_r, W2, b2, Wc, bc, w3, H, g, p_drop, seed):
         ctx.H, ctx.g, ctx.p_drop, ctx.seed = H, g, p_drop, seed
         E = g.row_ctx.shape[0]
-        save = EDGE_SAVE_FWD and X3_EDGE_SAVE_FWD and H >= EDGE_SAVE_MIN_H and E >= max(1, EDGE_SAVE_MIN_EDGES)
+        save = EDGE_SAVE_FWD and H >= EDGE_SAVE_MIN_H and E >= 1
         out = K.gcl_edge_fused_x3(AB, H, g.row_ctx, g.col_ctx, rhohat, w_r, W2, b2, Wc, bc, w3, AB.shape[0], p_drop, seed,
                                   rowptr=g.rp_ctx, save=save)
         ctx.n_saved = 3 if save else 0
@@ -874,9 +865,6 @@ class _FusedEdgeX3(torch.autograd.Function):
             AB.to(torch.bfloat16), ctx.H, g.row_ctx, g.col_ctx, rhohat, w_r, W2, b2, Wc, bc, w3, ds.reshape(-1).float(), dagg.float(),
             colptr, perm, ctx.p_drop, ctx.seed, dab_bf16=False, w_dtype=torch.float32, rowptr=g.rp_ctx, saved=saved)
         return (dAB, drh, dwr, dW2, db2, dWc, dbc, dw3, None, None, None, None)
-
-
-X3_EDGE_SAVE_FWD = os.environ.get("FABIND_X3_EDGE_SAVE_FWD", "1") != "0"    # 0: 'bf16x3' keeps the recompute backward (round 3-4; A/B)
 
 
 def fused_edge(AB16, rhohat, w_r, W2, b2, Wc, bc, w3, H, g, p_drop=0.0, frags=None):
@@ -1185,15 +1173,12 @@ class _PutRows(torch.autograd.Function):
         # itself, or a tensor created there) and nobody but the engine's frame and this Python wrapper references it -- a
         # producer that hands one gradient tensor to several edges (AddBackward on the pdrop > 0 paths) shows a higher use
         # count, and anything autograd summed or copied on the way has lost the mark.  Everything else gets a fresh tensor.
-        if PUT_ROWS_INPLACE_GRAD and dout.is_contiguous() and _owned_grad(dout):
+        if dout.is_contiguous() and _owned_grad(dout):
             d_base = dout
             d_base.index_fill_(0, idx, 0.0)
         else:
             d_base = dout.index_fill(0, idx, 0.0)
         return d_base, d_rows, None, None
-
-
-PUT_ROWS_INPLACE_GRAD = True
 
 
 def _owned_grad(g):
@@ -1251,7 +1236,7 @@ class GradSink:
         self.buf = None
         self.pending = None          # full-size fp32 tensor deferred by deposit()
         self.rows = []               # (index64, rows) deferred by deposit_rows()
-        self.deferred = []           # (A, Wt) input-gradient GEMMs held back by gemm_into() until `_SinkOwner.backward` (DEFER_DX)
+        self.deferred = []           # (A, Wt) input-gradient GEMMs held back by gemm_into() until `_SinkOwner.backward`
 
     def take(self, like):
         """-> (buffer, True if this call created it and must return it as the gradient)."""
@@ -1291,7 +1276,7 @@ class GradSink:
     def gemm_into(self, A, Wt, like, dtype=torch.float32):
         """d x (+)= A @ Wt^T-form GEMM (K.gemm(A, Wt)) into the shared buffer; returns the buffer if this call created it
         (the caller hands it to autograd), else None."""
-        if (DEFER_DX and A.dtype == torch.bfloat16 and Wt.dtype == torch.bfloat16 and A.dim() == 2 and A.stride(1) == 1 and A.stride(0) % 8 == 0
+        if (A.dtype == torch.bfloat16 and Wt.dtype == torch.bfloat16 and A.dim() == 2 and A.stride(1) == 1 and A.stride(0) % 8 == 0
                 and A.shape[1] % 64 == 0 and A.shape[0] >= DEFER_DX_MIN_ROWS and A.data_ptr() % 16 == 0):
             # held back: a tensor with two input-gradient GEMMs (first edge Linear + node MLP on h; k | v projection + Transition on the
             # attention update; pair projections + q | k | v on the attention layer's input) gets ONE launch over the K-concatenated
@@ -1315,8 +1300,7 @@ class GradSink:
         return None
 
 
-DEFER_DX = os.environ.get("FABIND_DEFER_DX", "1") == "1"     # 0: every input-gradient GEMM into a shared buffer is launched where it arises (round 4)
-DEFER_DX_MIN_ROWS = int(os.environ.get("FABIND_DEFER_DX_MIN_ROWS", "1024"))
+DEFER_DX_MIN_ROWS = 1024
 
 
 def _run_deferred(defs, out, base, accumulate):
@@ -1486,7 +1470,7 @@ class _PairHadamard(torch.autograd.Function):
         return d0_ret, d1, None, None, None, None, None
 
 
-PAIRHAD_ROWS = os.environ.get("FABIND_PAIRHAD_ROWS", "1") == "1"   # adjoint of the pair Hadamard as a row walk of the inter graph (no atomics)
+PAIRHAD_ROWS = _cfg.knob("FABIND_PAIRHAD_ROWS")   # adjoint of the pair Hadamard as a row walk of the inter graph (no atomics)
 
 
 def pair_hadamard(a0b0, H, ab32, H2, red_p, red_c, graph=None):
@@ -1569,7 +1553,7 @@ def _rows_hadamard_csr(ia, ib, n, a_sorted=False):
     return rowptr.to(torch.int32), pair_idx, partner
 
 
-ROWS_HADAMARD_WALK = os.environ.get("FABIND_ROWS_HADAMARD_WALK", "1") == "1"      # adjoint of rows_hadamard as a row walk (0: float atomics)
+ROWS_HADAMARD_WALK = _cfg.knob("FABIND_ROWS_HADAMARD_WALK")      # adjoint of rows_hadamard as a row walk (0: float atomics)
 
 
 def _block_hadamard_fwd(t, bl, n_a):
@@ -1668,7 +1652,7 @@ class _InterAttn(torch.autograd.Function):
             dpre, dbc = dcv, None
             if dcv.dtype != md:
                 in_tn = ctx.needs_input_grad[15] and ctx.needs_input_grad[16] and _db_in_tn(dcv)
-                dpre, dbc = _mul_dact_colsum(dcv, None, K.ACT_NONE, md) if (FUSE_DB and not in_tn) else (_mul_dact(dcv, None, K.ACT_NONE, md), None)
+                dpre, dbc = _mul_dact_colsum(dcv, None, K.ACT_NONE, md) if not in_tn else (_mul_dact(dcv, None, K.ACT_NONE, md), None)
             K.gemm(dpre, Wc.t().contiguous(), out=dqkv[:, 2 * H:], accumulate=True)
             if ctx.needs_input_grad[15] and ctx.needs_input_grad[16] and dbc is None:
                 dWc, dbc = _weight_grad(dpre, v_in, K.ACT_NONE, None, Wc.dtype, want_db=True, W=Wc)
@@ -1685,10 +1669,7 @@ class _InterAttn(torch.autograd.Function):
                 dw[2], dw[3], None, None, None, dcp[:E] if ctx.has_ext else None, dWc, dbc, None, None)
 
 
-INTER_BWD_BLOCKS = int(os.environ.get("FABIND_INTER_BWD_BLOCKS", "1024"))
-
-
-INTER_ATTN_INPLACE = os.environ.get("FABIND_INTER_ATTN_INPLACE", "1") == "1"
+INTER_BWD_BLOCKS = 1024
 
 
 def inter_attn(qkv, cv, H, h, x, d, rhohat, g, bias_part, w_rk, w_rv, wcr, w3, clampv, s_ext=None, Wc=None, bc=None, own_h=False, Wc32=None):
@@ -1709,7 +1690,7 @@ def inter_attn(qkv, cv, H, h, x, d, rhohat, g, bias_part, w_rk, w_rv, wcr, w3, c
     if cv is None:
         cv = linear(qkv[:, 2 * H:], Wc, bc, W32=Wc32)
     deal = getattr(g, "int_deal", None)
-    if own_h and INTER_ATTN_INPLACE and deal is not None and K.INTER_ATTN_ROWS and h.is_contiguous() and h.dtype == torch.float32 and not h.requires_grad:
+    if own_h and deal is not None and K.INTER_ATTN_ROWS and h.is_contiguous() and h.dtype == torch.float32 and not h.requires_grad:
         c = getattr(h, "_fab_b16", None)
         h16 = (c[1] if (c is not None and c[0] == h._version and c[1].is_contiguous()) else h.to(torch.bfloat16)) if w16 else None
         h_out, x_out, alpha, _ = K.inter_attn_fwd(qkv, cv, H, h, x, d, rhohat, g.rp_int, g.col_int, g.red_idx, bias_part,
@@ -1891,7 +1872,7 @@ class PairBias:
     def __init__(self, a0b0, H, wcomp, bconst, lay):
         self.a0b0, self.H, self.wcomp, self.bconst, self.lay = a0b0, H, wcomp, bconst, lay
         self._tensors, self._a16, self._bo = None, None, {}
-        self._bot, self._bw = {}, None            # fused backward: Bo^T packs per block; state shared by the blocks of one backward pass
+        self._bw = None                           # fused backward: state shared by the blocks of one backward pass
         self._n_fused = 0
         self._fused_blocks = set()                # blocks with a differentiable fused forward whose backward has not run yet
         # a differentiable pass will come (training: the last refinement iteration) and its backward cannot recompute the bias in the
@@ -1902,7 +1883,7 @@ class PairBias:
 
     def can_fuse(self):
         # (the kernels assume wcomp[k] rows ordered lin0..3 | gate0..3 for 4 heads of 32 channels: engine._stack_requests builds them so)
-        return (K.CROSS_ATTN_FUSED and _cfg.get_precision() == "bf16"
+        return (_cfg.get_precision() == "bf16"
                 and self.lay.max_C <= K.CROSS_ATTN_FUSED_MAX_C
                 and self.H in (64, 128, 256, 512) and tuple(self.wcomp.shape[1:]) == (8, self.H))
 
@@ -1916,12 +1897,6 @@ class PairBias:
 
     def has_tensors(self):
         return self._tensors is not None
-
-    def bot(self, k):
-        with torch.no_grad():
-            if not self._bot:
-                self._bot = dict(enumerate(K.pair_bot_pack(self.a0b0[:, self.H:], self.wcomp, self.H, self.lay)))
-        return self._bot[k]
 
     def tensors(self):
         if self._tensors is None:
@@ -1939,9 +1914,8 @@ class PairBias:
         return self._a16, bo, self._bc[k]
 
 
-ATTN_DA0_IN_KERNEL = os.environ.get("FABIND_ATTN_DA0_IN_KERNEL", "0") == "1"    # 1: d a0 contracted inside every block's backward kernel (A/B)
-FUSED_ATTN_TRAIN_MIN_TILES = int(os.environ.get("FABIND_ATTN_FUSED_TRAIN_MIN_TILES", "512"))
-FUSED_ATTN_TRAIN = os.environ.get("FABIND_ATTN_FUSED_TRAIN", "1") == "1"     # 0: the differentiable pass reads / writes [pairs, 8] bias tensors (round 3)
+FUSED_ATTN_TRAIN_MIN_TILES = 512
+FUSED_ATTN_TRAIN = _cfg.knob("FABIND_ATTN_FUSED_TRAIN")     # 0: the differentiable pass reads / writes [pairs, 8] bias tensors (round 3)
 _SLOT_TO_ROW = [0, 4, 1, 5, 2, 6, 3, 7]          # slot order of the packed operands (lin0, gate0, lin1, gate1, ...) -> row of wcomp / bconst (lin0..3, gate0..3)
 
 
@@ -1986,9 +1960,8 @@ class _CrossAttnFused(torch.autograd.Function):
         # uncovered rows (the ligand rows of a node-layout array) must read zero: they flow into the projections' adjoints
         dqg = (torch.zeros_like if mode == 0 else torch.empty_like)(qg)
         dkv = (torch.empty_like if mode == 0 else torch.zeros_like)(kv)
-        in_k = ATTN_DA0_IN_KERNEL
-        K.cross_attn_fused_bwd(qg, kv, a16, bo, pb.bot(k) if in_k else None, bc, lay, H, mode, ctx.scale, out, lse, dout, dqg, dkv,
-                               da0b0 if in_k else None, bw["acat"], k * Kp, bw["colpart"][:, k * NO:], Kp)
+        K.cross_attn_fused_bwd(qg, kv, a16, bo, bc, lay, H, mode, ctx.scale, out, lse, dout, dqg, dkv,
+                               bw["acat"], k * Kp, bw["colpart"][:, k * NO:], Kp)          # (d a0: the ragged GEMM of the last block)
         bw["done"].append(k)
         bw["left"] -= 1
         dw_ret = db_ret = None
@@ -2002,16 +1975,15 @@ class _CrossAttnFused(torch.autograd.Function):
             acat = bw["acat"]
             wslot = wcomp.float()[:, _SLOT_TO_ROW].contiguous()              # [nblk, 8, H], rows in the packed operands' slot order
             ran = sorted(bw["done"])
-            if not in_k:
-                # d a0 of ALL blocks as ONE ragged GEMM over the stored gradient rows (K = nblk x C x 8): the gradient is written once
-                if len(ran) != nblk:
-                    for kk in set(range(nblk)) - set(ran):
-                        acat[:, kk * Kp:(kk + 1) * Kp].zero_()
-                BTcat = torch.empty((lay.B * H, nblk * Kp), dtype=torch.bfloat16, device=dev)
-                check(load().fabind_pair_bias_btcat(ptr(a0b0[:, H:]), a0b0.stride(0), ptr(lay.c_index), ptr(lay.desc_p), ptr(wslot), nblk, H, Kp,
-                                                    ptr(BTcat), BTcat.stride(0), lay.B, stream()), "fabind_pair_bias_btcat")
-                K.gemm(acat, BTcat, out=da0b0, accumulate=True, groups=cat_g, n_groups=lay.B, max_m=lay.max_P, max_n=H,
-                       M=lay.sumP, N=lay.B * H, ldc=a0b0.stride(0), flops=2.0 * lay.n_pairs * NO * nblk * H)
+            # d a0 of ALL blocks as ONE ragged GEMM over the stored gradient rows (K = nblk x C x 8): the gradient is written once
+            if len(ran) != nblk:
+                for kk in set(range(nblk)) - set(ran):
+                    acat[:, kk * Kp:(kk + 1) * Kp].zero_()
+            BTcat = torch.empty((lay.B * H, nblk * Kp), dtype=torch.bfloat16, device=dev)
+            check(load().fabind_pair_bias_btcat(ptr(a0b0[:, H:]), a0b0.stride(0), ptr(lay.c_index), ptr(lay.desc_p), ptr(wslot), nblk, H, Kp,
+                                                ptr(BTcat), BTcat.stride(0), lay.B, stream()), "fabind_pair_bias_btcat")
+            K.gemm(acat, BTcat, out=da0b0, accumulate=True, groups=cat_g, n_groups=lay.B, max_m=lay.max_P, max_n=H,
+                   M=lay.sumP, N=lay.B * H, ldc=a0b0.stride(0), flops=2.0 * lay.n_pairs * NO * nblk * H)
             Dt = torch.empty((nblk, lay.B * Kp, Pp), dtype=torch.bfloat16, device=dev)
             At = torch.empty((lay.B * H, Pp), dtype=torch.bfloat16, device=dev)
             check(load().fabind_batched_transpose_pad(ptr(acat), acat.stride(0), ptr(lay.desc_p), lay.B, nblk, Kp, Pp, ptr(Dt), stream()),

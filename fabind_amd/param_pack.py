@@ -10,12 +10,12 @@ writing every parameter gradient slice.  Products of parameters (composed weight
 
 A parameter element may appear in at most ONE request (its gradient slice is written, not accumulated): the builders in engine.py
 keep to that, and `FABIND_PARAM_PACK=check` verifies it on every call."""
-import os
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import config as _cfg
 from ._lib import check, dt_code, stream
 
 _SEG = np.dtype([("src", np.uint64), ("dst", np.uint64), ("src_sr", np.int64), ("src_sc", np.int64), ("dst_sr", np.int64),
@@ -274,7 +274,7 @@ class ParamPack:
         starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         rows, req, rel, esz = [], [], [], []
         t_reqs = set(self.t_of.values())
-        check_overlap = os.environ.get("FABIND_PARAM_PACK", "") == "check"
+        check_overlap = _cfg.param_pack() == "check"
         cover = [np.zeros(n, dtype=np.int8) for n in sizes] if check_overlap else None
         for k_req, ((nd, dtype, dim, pieces), (oshape, offs)) in enumerate(zip(self.reqs, self._lay)):
             if k_req in t_reqs:                          # (nothing differentiates through the transposed copies)

@@ -16,11 +16,11 @@ The kernels are the generic ones (GEMM, row LayerNorm, cross attention, inter-ed
 bf16 inference / sampling, one fused pair-update kernel per layer (csrc/pair_fused.hip); under autograd the pair update
 runs as separate Hadamard / GEMM / LayerNorm launches."""
 import math
-import os
 
 import numpy as np
 import torch
 
+from .. import config as _cfg
 from .. import kernels as K
 from .. import ops
 from ..config import fp32_storage, get_precision
@@ -205,7 +205,6 @@ def att_params(m):
 
 
 _PLAN_CACHE = {}           # id(model) -> (key, ParamPack with its requests, request tree, weakref(model))
-PLUS_PARAM_PACK = os.environ.get("FABIND_PLUS_PARAM_PACK", "1") == "1"     # training: one-launch differentiable pack (0: torch ops per entry)
 
 
 def _stack_requests(model, pk):
@@ -232,7 +231,7 @@ def _build_stack_params(model):
     are planned once per model and re-run every step (v1: engine._build_stack_params)."""
     gnn = model.gnn
     H, L = gnn.hidden_nf, gnn.n_layers
-    if not (torch.is_grad_enabled() and PLUS_PARAM_PACK and os.environ.get("FABIND_PARAM_PACK", "1") != "0"):
+    if not (torch.is_grad_enabled() and _cfg.param_pack() != "0"):
         P = {"H": H, "L": L}
         wd = _wd()
         W = lambda t: t.to(wd).contiguous()
@@ -252,7 +251,7 @@ def _build_stack_params(model):
     params = _e.last_params_of(model)
     key = (_wd(), tuple((id(p_), p_.data_ptr(), p_.requires_grad) for p_ in params))
     ent = _PLAN_CACHE.get(id(model))
-    if ent is not None and ent[0] == key and ent[3]() is model and _e.PACK_PLAN:
+    if ent is not None and ent[0] == key and ent[3]() is model:
         pk, tree = ent[1], ent[2]
     else:
         import weakref
@@ -416,7 +415,7 @@ class _PairHad1(torch.autograd.Function):
         Hh, lay = ctx.Hh, ctx.lay
         dhd = dhd.contiguous()
         dT = torch.zeros_like(T)
-        if (lay is not None and PAIRHAD_GRID and T.dtype == torch.float32 and p_node.shape[0] == lay.n_pairs and Hh % 4 == 0
+        if (lay is not None and T.dtype == torch.float32 and p_node.shape[0] == lay.n_pairs and Hh % 4 == 0
                 and (Hh >= 256 or 256 % Hh == 0) and T.stride(0) % 4 == 0 and dhd.stride(0) % 4 == 0):
             # the list is the batch's full protein x ligand grid: deterministic row walk instead of float atomics (csrc/bwd.hip)
             nb = getattr(lay, "_node_b", None)
@@ -434,9 +433,6 @@ class _PairHad1(torch.autograd.Function):
                                               ptr(db), dT.stride(0), ptr(da), ptr(db), dT.stride(0), stream()),
               "fabind_pair_hadamard_bwd")
         return dT, None, None, None, None, None
-
-
-PAIRHAD_GRID = os.environ.get("FABIND_PAIRHAD_GRID", "1") == "1"     # adjoint of the all-pairs Hadamard as a row walk (no float atomics)
 
 
 def pair_had(T, Hh, p_node, c_node, out_dtype, lay=None):
@@ -491,12 +487,6 @@ class _InterView:
 # ------------------------------------------------------------------------------------------------
 # layers
 # ------------------------------------------------------------------------------------------------
-MLP2_NODE = os.environ.get("FABIND_PLUS_MLP2_NODE", "1") == "1"      # training: the two Linears of an LN-MLP as one autograd node (ops._MLP2Relu)
-Z_SINK = os.environ.get("FABIND_PLUS_Z_SINK", "1") == "1"             # training: shared gradient buffer for the pair embedding of every layer
-ROWDOT_DROP_GRAD = os.environ.get("FABIND_PLUS_ROWDOT_DROP", "1") == "1"   # training: coord-MLP row-dot with its dropout inside the GEMM epilogue
-EPI_DROP_GRAD = os.environ.get("FABIND_EPI_DROP_GRAD", "1") == "1"   # training: ReLU + dropout inside the GEMM epilogue (no torch mask kernels)
-
-
 def _drop(t, pr):
     """nn.Dropout of the reference modules (train mode = FABind+ sampling inference): element-wise mask + scale between
     kernels, torch's generator."""
@@ -509,7 +499,7 @@ def ln_mlp(m, x, last_act, residual=None, out_dtype=torch.float32, pdrop=0.0):
     ad = ops.act_dtype()
     y = ln_rows(x, m["ln_w"], m["ln_b"], ad, m["k_pad"]) if m["ln_w"] is not None else x
     act2 = K.ACT_RELU if last_act else K.ACT_NONE
-    if (MLP2_NODE and (pdrop == 0.0 or EPI_DROP_GRAD) and ops.needs_grad(y, m["W1"], m["W2"], residual)
+    if (ops.needs_grad(y, m["W1"], m["W2"], residual)
             and y.dtype == torch.bfloat16 and m["W1"].dtype == torch.bfloat16 and m["b1"] is not None and m["b2"] is not None
             and m["W1"].shape[0] % 8 == 0 and m["W2"].shape[0] % 8 == 0):
         # both Linears as one autograd node (ops._MLP2Relu); relu + dropout ahead of a residual: the node returns the dropped
@@ -521,13 +511,11 @@ def ln_mlp(m, x, last_act, residual=None, out_dtype=torch.float32, pdrop=0.0):
     if pdrop > 0.0 and ops.needs_grad(y, m["W1"], m["W2"], residual):
         # under autograd the ReLU + dropout pairs run inside the GEMM epilogue too (ops._Linear: the zeros of the saved output are the
         # dropped positions); only a dropout that is followed by a residual keeps the torch mask
-        t = ops.linear(y, m["W1"], m["b1"], act_epi=K.ACT_RELU, out_dtype=ad, p_drop=pdrop if EPI_DROP_GRAD else 0.0)
-        t = t if EPI_DROP_GRAD else _drop(t, pdrop)
+        t = ops.linear(y, m["W1"], m["b1"], act_epi=K.ACT_RELU, out_dtype=ad, p_drop=pdrop)
         if last_act:
-            if residual is None and EPI_DROP_GRAD:
+            if residual is None:
                 return ops.linear(t, m["W2"], m["b2"], act_epi=act2, out_dtype=out_dtype, p_drop=pdrop)
-            y2 = _drop(ops.linear(t, m["W2"], m["b2"], act_epi=act2), pdrop)
-            return (y2 if residual is None else residual + y2).to(out_dtype)
+            return (residual + _drop(ops.linear(t, m["W2"], m["b2"], act_epi=act2), pdrop)).to(out_dtype)
         return ops.linear(t, m["W2"], m["b2"], act_epi=act2, residual=residual, out_dtype=out_dtype)
     t = ops.linear(y, m["W1"], m["b1"], act_epi=K.ACT_RELU, out_dtype=ad, p_drop=pdrop)
     return ops.linear(t, m["W2"], m["b2"], act_epi=act2, residual=residual, out_dtype=out_dtype,
@@ -537,7 +525,7 @@ def ln_mlp(m, x, last_act, residual=None, out_dtype=torch.float32, pdrop=0.0):
 def lin_drop(x, W, b, residual, pd):
     """residual + dropout(x W^T + b) with the dropout inside the GEMM's fp32 epilogue; under autograd the adjoint regenerates the
     counter-based mask (round 5: ops._Linear) -- a torch mask only for a residual that is not fp32."""
-    if pd > 0.0 and ops.needs_grad(x, W, b, residual) and not (EPI_DROP_GRAD and residual.dtype == torch.float32 and W.shape[0] % 4 == 0):
+    if pd > 0.0 and ops.needs_grad(x, W, b, residual) and not (residual.dtype == torch.float32 and W.shape[0] % 4 == 0):
         return residual + _drop(ops.linear(x, W, b), pd)
     return ops.linear(x, W, b, residual=residual, p_drop=pd)
 
@@ -552,10 +540,6 @@ def _coord_scalar(c, v, pd):
         mu, rs = K.row_stats(v, fp["eps"])
         return ops.linear_rowdot(v, fp["W1w"], fp["dvec"], c["w3"], act_epi=K.ACT_RELU, p_drop=pd, fold=(mu, rs, fp["cvec"]))
     yc = ln_rows(v, c["ln_w"], c["ln_b"], ad, c["k_pad"])
-    if pd > 0.0 and ops.needs_grad(yc, c["W1"], c["w3"]) and not (EPI_DROP_GRAD and ROWDOT_DROP_GRAD):
-        tc = ops.linear(yc, c["W1"], c["b1"], act_epi=K.ACT_RELU, p_drop=pd) if EPI_DROP_GRAD else \
-            _drop(ops.linear(yc, c["W1"], c["b1"], act_epi=K.ACT_RELU), pd)
-        return (tc * c["w3"]).sum(1, keepdim=True)
     return ops.linear_rowdot(yc, c["W1"], c["b1"], c["w3"], act_epi=K.ACT_RELU, p_drop=pd)
 
 
@@ -580,14 +564,11 @@ def gcl_layer(p, h, x, lay, g, clampv, pd=0.0):
     elif grad:     # the concatenation is materialised so that LayerNorm is a separate differentiable step
         cat = _EdgeConcat.apply(h, rhohat, g.row_ctx, g.col_ctx, g.rp_ctx, g.ctx_by_col, ad, e["k_pad"])
         y = ln_rows(cat[:, :2 * H + 1], e["ln_w"], e["ln_b"], ad, e["k_pad"])
-        if MLP2_NODE and EPI_DROP_GRAD and y.dtype == torch.bfloat16 and e["W1"].dtype == torch.bfloat16:
+        if y.dtype == torch.bfloat16 and e["W1"].dtype == torch.bfloat16:
             m = ops.mlp2_relu(y, e["W1"], e["b1"], e["W2"], e["b2"], True, None, ad, pd)
-        elif EPI_DROP_GRAD:
+        else:
             t = ops.linear(y, e["W1"], e["b1"], act_epi=K.ACT_RELU, out_dtype=ad, p_drop=pd)
             m = ops.linear(t, e["W2"], e["b2"], act_epi=K.ACT_RELU, out_dtype=ad, p_drop=pd)
-        else:
-            t = _drop(ops.linear(y, e["W1"], e["b1"], act_epi=K.ACT_RELU, out_dtype=ad), pd)
-            m = _drop(ops.linear(t, e["W2"], e["b2"], act_epi=K.ACT_RELU, out_dtype=ad), pd)
     elif FOLD_EDGE_LN and "fold" in p:
         # inference, bf16: W1 LN([h_r | h_c | rho]) from per-node projections and per-node statistics -- the
         # [E, 2H+1] x [2H+1, 2H+1] contraction becomes one [N, H] x [H, 2(2H+1)] contraction and a gather
@@ -612,9 +593,9 @@ def gcl_layer(p, h, x, lay, g, clampv, pd=0.0):
     return h_new, x_new
 
 
-FUSE_PAIR = os.environ.get("FABIND_PLUS_FUSE_PAIR", "1") == "1"
-FOLD_EDGE_LN_TRAIN = os.environ.get("FABIND_PLUS_FOLD_EDGE_LN_TRAIN", "1") == "1"     # 0: under autograd concat -> LayerNorm -> GEMM (rounds 1-4; A/B)
-FOLD_EDGE_LN = os.environ.get("FABIND_PLUS_FOLD_EDGE_LN", "1") == "1"
+FUSE_PAIR = _cfg.knob("FABIND_PLUS_FUSE_PAIR")            # 0: the pair update of no-grad bf16 passes as separate kernels (A/B)
+FOLD_EDGE_LN_TRAIN = _cfg.knob("FABIND_PLUS_FOLD_EDGE_LN_TRAIN")     # 0: under autograd concat -> LayerNorm -> GEMM (rounds 1-4; A/B)
+FOLD_EDGE_LN = _cfg.knob("FABIND_PLUS_FOLD_EDGE_LN")         # 0: no LayerNorm-folded edge / coordinate Linears (A/B)
 
 
 def cross_part(p, h, z, lay, pairs, pd=0.0, bias=None, p_next=None):
@@ -653,8 +634,7 @@ def cross_part(p, h, z, lay, pairs, pd=0.0, bias=None, p_next=None):
         hd32 = pair_had(ab32, 64, pairs.p_node, pairs.c_node, ad, lay)                               # [pairs, 64]
         z1 = ops.linear(hd32, p["W_o32"], p["b_o32"], residual=z, out_dtype=ad)      # (a bf16 z is added as it is: FabindGemmArgs.r_dtype)
         z = ln_mlp(p["tr_z"], z1, True, out_dtype=ad, pdrop=pd)
-        if Z_SINK:      # consumers: the inter-edge row gather, the next layer's pair-bias Linear and its residual: one gradient buffer
-            z = ops.shared_grad(z)
+        z = ops.shared_grad(z)      # consumers: the inter-edge row gather, the next layer's pair-bias Linear and its residual: one gradient buffer
     return h, z, bias_next
 
 
@@ -693,7 +673,7 @@ def att_layer(p, h, x, z, lay, g, pairs, batch_id, clampv, pd=0.0, bias=None, p_
 def egnn_forward(P, h, x, z0, lay, g, las, x_las, pairs, batch_id, scale, step, capture=None, pd=0.0):
     clampv = 10.0 / scale
     h = ops.linear(h, P["W_in"], P["b_in"], p_drop=pd)      # (dropout in the fp32 epilogue; under autograd the adjoint regenerates the mask)
-    z, bias = (ops.shared_grad(z0) if Z_SINK else z0), None
+    z, bias = ops.shared_grad(z0), None
     for i in range(P["L"]):
         h, x = gcl_layer(P["gcl"][i], h, x, lay, g, clampv, pd)
         if capture is not None:

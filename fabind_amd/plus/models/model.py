@@ -292,12 +292,9 @@ class FABindPlus(nn.Module):
         wd = ops.mm_dtype()
         y = pengine.ln_rows(zz, m.layernorm.weight.float(), m.layernorm.bias.float(), ops.act_dtype())
         pd = self._pd()
-        if pd > 0.0 and ops.needs_grad(y) and not (pengine.EPI_DROP_GRAD and pengine.ROWDOT_DROP_GRAD):
-            t = pengine._drop(ops.linear(y, m.linear1.weight.to(wd).contiguous(), m.linear1.bias, act_epi=K.ACT_RELU), pd)
-            part = (t * m.linear2.weight[0].float()).sum(1, keepdim=True)
-        else:       # (under autograd with dropout: the row-dot node with the dropout inside the GEMM epilogue, ops._LinearRowdotDrop)
-            part = ops.linear_rowdot(y, m.linear1.weight.to(wd).contiguous(), m.linear1.bias,
-                                     m.linear2.weight[0].float().contiguous(), act_epi=K.ACT_RELU, p_drop=pd)
+        # (under autograd with dropout: the row-dot node with the dropout inside the GEMM epilogue, ops._LinearRowdotDrop)
+        part = ops.linear_rowdot(y, m.linear1.weight.to(wd).contiguous(), m.linear1.bias,
+                                 m.linear2.weight[0].float().contiguous(), act_epi=K.ACT_RELU, p_drop=pd)
         thres = self.args.dis_map_thres
         y_pred = (part.sum(1) + m.linear2.bias).sigmoid() * thres
         cb = data['compound'].batch

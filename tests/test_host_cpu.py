@@ -459,3 +459,158 @@ def test_bench_dump_outputs_budget_and_sampling(tmp_path):
     assert np.isin(s[::1009], big.numpy().reshape(-1)).all()               # a sample of the tensor's own elements
     for f in files:
         assert (np.load(dirs[1] / f) == ld[f[:-4]]).all()                   # the same sample on every call
+
+
+# ------------------------------------------------------------------------------------------------
+# the table of FABIND_* environment variables (fabind_amd/config.py)
+# ------------------------------------------------------------------------------------------------
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _package_sources():
+    for dirpath, _, files in os.walk(os.path.join(_ROOT, "fabind_amd")):
+        for f in sorted(files):
+            if f.endswith(".py"):
+                path = os.path.join(dirpath, f)
+                yield os.path.relpath(path, os.path.join(_ROOT, "fabind_amd")), open(path).read()
+
+
+def test_environment_is_read_in_config_and_build_only():
+    """No module of the package but config.py (the table) and build.py (HIPCC) looks at the process environment."""
+    seen = 0
+    for rel, src in _package_sources():
+        seen += 1
+        if rel not in ("config.py", "build.py"):
+            assert not re.search(r"os\.environ|getenv", src), rel
+    assert seen >= 20
+
+
+def test_every_fabind_literal_is_in_the_table_and_every_table_name_is_read():
+    """Every "FABIND_..." string literal of the package is a name of config.KNOBS (a typo would read nothing, silently), and every name
+    of the table is consumed: by a config.knob("NAME") / config.read("NAME", ...) call, or -- 'native-dev' -- by the loop of _lib.load(),
+    which needs a void setter that _lib declares."""
+    import ast
+    from fabind_amd import config
+    read, lib_src = set(), None
+    for rel, src in _package_sources():
+        if rel == "_lib.py":
+            lib_src = src
+        for node in ast.walk(ast.parse(src)):
+            if isinstance(node, ast.Constant) and isinstance(node.value, str) and re.fullmatch(r"FABIND_[A-Z0-9_]+", node.value):
+                assert node.value in config.KNOBS, (rel, node.value)
+            if isinstance(node, ast.Call) and getattr(node.func, "attr", getattr(node.func, "id", None)) in ("knob", "read") and node.args \
+                    and isinstance(node.args[0], ast.Constant):
+                read.add(node.args[0].value)
+    with pytest.raises(KeyError):
+        config.knob("FABIND_NO_SUCH_KNOB")
+    assert "native-dev" in lib_src and "k.setter" in lib_src
+    for k in config.KNOBS.values():
+        assert k.category in ("mode-seed", "ab", "native-dev", "debug") and k.type in (bool, int, str) and k.doc, k.name
+        if k.category == "native-dev":
+            assert k.default is None and k.type is int and '"%s"' % k.setter in lib_src, k.name
+        else:
+            assert k.name in read, k.name
+
+
+def test_knob_attributes_exist_where_the_table_says():
+    """The module attributes tests and probes assign are initialised from the table, under the names the table records."""
+    import importlib
+    from fabind_amd import config
+    for k in config.KNOBS.values():
+        if k.category == "mode-seed":
+            continue
+        mod, name = k.attr.rsplit(".", 1)
+        assert hasattr(importlib.import_module("fabind_amd." + mod), name), k
+        if k.type is bool and mod != "_lib":
+            assert getattr(importlib.import_module("fabind_amd." + mod), name) is config.knob(k.name), k.name
+
+
+def test_knobs_document_agrees_with_the_table():
+    """docs/KNOBS.md: the A/B section is the table config.knobs_markdown() prints (names, defaults, notes); the mode seeds are named in
+    the numerics section."""
+    from fabind_amd import config
+    doc = open(os.path.join(_ROOT, "docs", "KNOBS.md")).read()
+    modes, ab = doc.split("## A/B knobs")
+    rows = [ln for ln in ab.splitlines() if ln.startswith("|")]
+    assert rows == config.knobs_markdown().splitlines()
+    got = {m.group(1): m.group(2) for m in (re.match(r"\| `(FABIND_\w+)` \| `?([^`|]*?)`? \|", ln) for ln in rows) if m}
+    want = {k.name: ("unset" if k.default in (None, "") else str(int(k.default) if k.type is bool else k.default))
+            for k in config.KNOBS.values() if k.category != "mode-seed"}
+    assert got == want
+    assert set(re.findall(r"FABIND_\w+", modes)) == {k.name for k in config.KNOBS.values() if k.category == "mode-seed"}
+
+
+def test_every_ab_knob_is_exercised_by_a_test_or_a_tool():
+    """An 'ab' / 'native-dev' knob stays in the product path only while a test or a tool drives its non-default side: `exercised_by` is
+    an existing file under tests/ or tools/ -- no retired probe, no script of a single past round -- that names the variable, the module
+    attribute it initialises, or the native setter."""
+    from fabind_amd import config
+    n = 0
+    for k in config.KNOBS.values():
+        if k.category not in ("ab", "native-dev"):
+            assert k.exercised_by is None, k.name
+            continue
+        n += 1
+        ex = k.exercised_by
+        assert ex and (ex.startswith("tests/") or ex.startswith("tools/")) and not ex.startswith("tools/probes/retired/"), k
+        assert not re.match(r"r\d+_", os.path.basename(ex)), k
+        text = open(os.path.join(_ROOT, ex)).read()
+        assert k.name in text or re.search(r"\b%s\b" % re.escape(k.attr.rsplit(".", 1)[1]), text) or (k.setter and k.setter in text), k
+    assert n >= 10
+
+
+def test_knob_reader_keeps_the_spellings_of_the_scattered_reads():
+    """config.read against the expressions the modules used before the table existed, for an unset variable, "0", "1" (and "check",
+    "2", a word): a process started with the same environment takes the same sides."""
+    from fabind_amd import config
+    eq1 = lambda n, d: (lambda e: e.get(n, d) == "1")
+    unless0 = lambda n: (lambda e: e.get(n, "1") != "0")
+    int_if_set = lambda n: (lambda e: int(e[n]) if e.get(n) else None)
+    old = {
+        "FABIND_X3_WGRAD": lambda e: e.get("FABIND_X3_WGRAD", "bf16"),
+        "FABIND_X3_PAIRBIAS_BWD": lambda e: e.get("FABIND_X3_PAIRBIAS_BWD", "bf16"),
+        "FABIND_X3_EDGE": lambda e: e.get("FABIND_X3_EDGE", "split"),
+        "FABIND_SPLIT_SITES": lambda e: int(e.get("FABIND_SPLIT_SITES", "3")),
+        "FABIND_ATTN_FUSED_TRAIN": eq1("FABIND_ATTN_FUSED_TRAIN", "1"),
+        "FABIND_EDGE_SAVE_FWD": unless0("FABIND_EDGE_SAVE_FWD"),
+        "FABIND_FUSE_DB_TN": eq1("FABIND_FUSE_DB_TN", "1"),
+        "FABIND_INTER_ATTN_ROWS": eq1("FABIND_INTER_ATTN_ROWS", "1"),
+        "FABIND_LAYOUT_CACHE": lambda e: not e.get("FABIND_LAYOUT_CACHE", "1") == "0",
+        "FABIND_PAIRHAD_ROWS": eq1("FABIND_PAIRHAD_ROWS", "1"),
+        "FABIND_PARAM_PACK": lambda e: e.get("FABIND_PARAM_PACK", "1"),
+        "FABIND_PLUS_FOLD_EDGE_LN": eq1("FABIND_PLUS_FOLD_EDGE_LN", "1"),
+        "FABIND_PLUS_FOLD_EDGE_LN_TRAIN": eq1("FABIND_PLUS_FOLD_EDGE_LN_TRAIN", "1"),
+        "FABIND_PLUS_FUSE_PAIR": eq1("FABIND_PLUS_FUSE_PAIR", "1"),
+        "FABIND_ROWS_HADAMARD_WALK": eq1("FABIND_ROWS_HADAMARD_WALK", "1"),
+        "FABIND_TN_DEFER": eq1("FABIND_TN_DEFER", "1"),
+        "FABIND_EDGE_BWD3_EXP": int_if_set("FABIND_EDGE_BWD3_EXP"),
+        "FABIND_EDGE_BWD_VARIANT": lambda e: int(e["FABIND_EDGE_BWD_VARIANT"]) if "FABIND_EDGE_BWD_VARIANT" in e else None,
+        "FABIND_GEMM_SMALL_M": int_if_set("FABIND_GEMM_SMALL_M"),
+        "FABIND_TN_WAVES": int_if_set("FABIND_TN_WAVES"),
+        "FABIND_DEBUG_GRAPH": eq1("FABIND_DEBUG_GRAPH", "0"),
+        "FABIND_DEBUG_SYNC": eq1("FABIND_DEBUG_SYNC", "0"),
+        "FABIND_LIB": lambda e: e.get("FABIND_LIB") or "",
+    }
+    assert set(old) == set(config.KNOBS)
+    for name, expr in old.items():
+        k = config.KNOBS[name]
+        spellings = [None, "0", "1", "2"] + ([] if k.type is int else ["check", "bf16", "x3"]) + ([""] if k.type is not int else [])
+        for v in spellings:
+            env = {"FABIND_UNRELATED": "1"} if v is None else {name: v}
+            assert config.read(name, env) == expr(env) and type(config.read(name, env)) is type(expr(env)), (name, v)
+    # the four call sites of FABIND_PARAM_PACK compared to "0" (torch ops), != "0" (the pack) and "check": one string serves them all
+    for v, eager, check in ((None, False, False), ("0", True, False), ("1", False, False), ("check", False, True)):
+        got = config.read("FABIND_PARAM_PACK", {} if v is None else {"FABIND_PARAM_PACK": v})
+        assert ((got == "0"), (got == "check")) == (eager, check)
+    with pytest.raises(KeyError):
+        config.read("FABIND_NO_SUCH_KNOB", {})
+
+
+def test_param_pack_switch_is_read_at_call_time(monkeypatch):
+    from fabind_amd import config
+    monkeypatch.delenv("FABIND_PARAM_PACK", raising=False)
+    assert config.param_pack() == "1"
+    monkeypatch.setenv("FABIND_PARAM_PACK", "check")
+    assert config.param_pack() == "check"
+    monkeypatch.setenv("FABIND_PARAM_PACK", "0")
+    assert config.param_pack() == "0"

@@ -1,10 +1,11 @@
 """Fused edge kernels at the bench shape (64 x 1500/40, H = 512): live HIP-event time per launch of the plain / saving forward and of the
-recompute / saved-forward backward kernels (kernels._profiled labels), n launches each.  FABIND_LIB selects an A/B build."""
+recompute / saved-forward backward kernels (kernels._profiled labels), n launches each.  FABIND_LIB selects an A/B build.
+usage: edge_bwd4_time.py [n [all|old|new [mask]]] -- mask: sensitivity mask of the saved-forward backward (results wrong: timing only)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 import bench
-from fabind_amd import engine, kernels as K
+from fabind_amd import _lib, engine, kernels as K
 dev = torch.device("cuda:0")
 engine.set_precision("bf16")
 n_prot = int(os.environ.get("N_PROT", "1500"))
@@ -23,6 +24,8 @@ colptr, perm = g.ctx_by_col()
 W2p, Wcp = K.pack_frag(W2), K.pack_frag(Wc)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 which = sys.argv[2] if len(sys.argv) > 2 else "all"
+if len(sys.argv) > 3:
+    _lib.load().fabind_gcl_edge_fused_bwd4_set_exp(int(sys.argv[3]))
 for rep in range(2):
     K.PROFILE = {} if rep else None
     for _ in range(n if rep else 2):

@@ -58,6 +58,12 @@ class AttnFusedBwdArgs(ctypes.Structure):
                [(n, _i) for n in ("nsplit", "B", "part_rows")]
 
 
+class AdamRow(ctypes.Structure):
+    """Mirror of FabindAdamRow (include/fabind_hip.h): one tensor of a fused Adam / AdamW step."""
+    _fields_ = [(n, _vp) for n in ("p", "g", "m", "v")] + [("numel", ctypes.c_longlong), ("chunk0", _i), ("step_idx", _i)] + \
+               [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("decoupled", _i), ("pad_", _i)]
+
+
 # name -> argtypes (every function returns int and takes the stream last)
 SIGNATURES = {
     "fabind_gemm": [ctypes.POINTER(GemmArgs), _vp],
@@ -95,6 +101,9 @@ SIGNATURES = {
     "fabind_sym_automorphisms": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_sym_score": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_multi_copy": [_vp, _i, _i, _vp],
+    "fabind_adam_chunk": [],
+    "fabind_multi_sqnorm": [_vp, _i, _i, _vp, _vp, _vp, _vp],
+    "fabind_multi_adam": [_vp, _i, _i, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp],
     "fabind_zero_empty_rows": [_vp, _i, _vp, _i, _i, _i, _vp, _i, _i, _vp],
     "fabind_split_sum": [_vp, _i, ctypes.c_long, _vp, _i, ctypes.c_long, _vp, _vp],
     "fabind_segment_sum": [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp],
@@ -193,7 +202,7 @@ def load():
     lib.fabind_loss_blocks.argtypes, lib.fabind_loss_blocks.restype = [_l, _l, _l], ctypes.c_int
     for nm in ("fabind_pair_block_tile", "fabind_pair_block_chunk"):
         getattr(lib, nm).argtypes, getattr(lib, nm).restype = [], ctypes.c_int
-    for which, mirror in enumerate((GemmArgs, EdgeBwdArgs, PairUpdateArgs, TnJob, AttnFusedBwdArgs)):
+    for which, mirror in enumerate((GemmArgs, EdgeBwdArgs, PairUpdateArgs, TnJob, AttnFusedBwdArgs, AdamRow)):
         if lib.fabind_sizeof_args(which) != ctypes.sizeof(mirror):
             raise RuntimeError("fabind_amd: ctypes mirror %s is %d bytes, the library's struct is %d -- _lib.py and "
                                "include/fabind_hip.h disagree" % (mirror.__name__, ctypes.sizeof(mirror),

@@ -18,6 +18,7 @@ extern "C" int fabind_sizeof_args(int which) {
         case 2: return (int)sizeof(FabindPairUpdateArgs);
         case 3: return (int)sizeof(FabindTnJob);
         case 4: return (int)sizeof(FabindAttnFusedBwdArgs);
+        case 5: return (int)sizeof(FabindAdamRow);
         default: return -1;
     }
 }

@@ -362,7 +362,9 @@ def train_step(model, data, optimizer, compute_loss, world=1, clip=1.0, stage=1,
     clip, optimizer step (main_fabind.py:392-426).  Returns (loss, terms) or None when the batch is skipped -- on ALL
     ranks together (the NaN flag is all-reduced first, so no rank is left waiting in the gradient collective).
     reducer: a GradReducer over the model's parameters (overlaps the all-reduce with backward); without one the
-    gradients are reduced after backward."""
+    gradients are reduced after backward.
+    optimizer: an `optim.FusedAdam` takes the clip into its own step (no `clip_grad_norm_` pass; .grad keeps the unclipped gradient);
+    every other optimizer is clipped and stepped as the reference does."""
     out = model(data, stage=stage, train=True)
     bad = torch.stack([torch.isnan(t).any() for t in (out[0], out[2], out[3], out[4], out[8])]).any()
     if all_ranks_agree_to_skip(bad, world):
@@ -375,7 +377,11 @@ def train_step(model, data, optimizer, compute_loss, world=1, clip=1.0, stage=1,
         reducer.finish()
     else:
         allreduce_gradients(params, world)
-    if clip:
-        clip_grad_norm_(params, clip)
-    optimizer.step()
+    from .optim import FusedAdam
+    if isinstance(optimizer, FusedAdam):
+        optimizer.step(max_grad_norm=clip or None)         # clip, non-finite guard and update: two launches (.grad is left unscaled)
+    else:
+        if clip:
+            clip_grad_norm_(params, clip)
+        optimizer.step()
     return loss.detach(), {k: v.detach() for k, v in terms.items()}

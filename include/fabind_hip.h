@@ -70,11 +70,14 @@ const char* fabind_last_error(void);
  *     Backward-compatible additions under 18: fabind_sym_automorphisms / fabind_sym_score (ligand automorphisms, symmetry-corrected RMSD).
  * 19 = fabind_las_step writes a per-node clamp mask (new argument pass_mask), fabind_las_step_bwd takes it in place of x_out: the adjoint's
  *     clamp decision is the forward's own (it used to be inferred from x_out - x, which fp32 rounding falsifies).
+ *     Backward-compatible additions under 19: fabind_multi_sqnorm / fabind_multi_adam + FabindAdamRow, fabind_adam_chunk (the fused Adam / AdamW
+ *     step with global-norm clip and non-finite skip; fabind_sizeof_args(5) = sizeof(FabindAdamRow)).  Purely additive: no existing entry
+ *     point or struct changed, so the version stays.
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
 /* sizeof() of an argument struct as this library was compiled: which = 0 FabindGemmArgs, 1 FabindEdgeBwdArgs,
- * 2 FabindPairUpdateArgs, 3 FabindTnJob (-1 for an unknown index).  Lets a foreign-language mirror of the struct verify its layout. */
+ * 2 FabindPairUpdateArgs, 3 FabindTnJob, 4 FabindAttnFusedBwdArgs, 5 FabindAdamRow (-1 for an unknown index).  Lets a foreign-language mirror of the struct verify its layout. */
 int fabind_sizeof_args(int which);
 
 /* ---------------------------------------------------------------------------------------------
@@ -182,6 +185,33 @@ typedef struct FabindCopySeg {
     int vec4, pad_;
 } FabindCopySeg;
 int fabind_multi_copy(const FabindCopySeg* segs_dev, int n_segs, int blocks_per_seg, hipStream_t stream);
+/* Fused Adam / AdamW step over many fp32 tensors with the global-norm clip and a non-finite guard folded in: two launches per step.
+ * Replaces torch.nn.utils.clip_grad_norm_ + torch.optim.Adam / AdamW.step() after backward (reference main_fabind.py:257-260, 419-426).
+ * One DEVICE table of rows, one per tensor that has a gradient this step, sorted by chunk0: a tensor is cut into chunks of
+ * fabind_adam_chunk() elements and row r owns chunks [chunk0[r], chunk0[r + 1]) of n_chunks (chunk0[0] = 0, numel >= 1).  All four
+ * tensors are contiguous fp32 of numel elements, 4-byte aligned (16-byte accesses are used where the addresses allow; the result does
+ * not depend on the alignment).  Hyper-parameters are doubles, as torch holds them; step_idx indexes the fp32 step-counter vector.
+ *   fabind_multi_sqnorm: partials[c] = sum of g^2 over chunk c (fixed order, no atomics); snap[r] = steps[step_idx[r]].
+ *   fabind_multi_adam:   total_norm = sqrt(sum_c partials[c]) (double, one fixed order in every block) -> *grad_norm;
+ *       flags bit 0: g is scaled by min(1, max_norm / (total_norm + 1e-6)); bit 1: a non-finite total_norm skips the step (nothing of
+ *       p / m / v / steps is written, *skipped += 1).  Otherwise torch 2.10's single-tensor Adam arithmetic with t = snap[r] + 1, and
+ *       steps[step_idx[r]] = snap[r] + 1.  g is only read: the clip does not rescale it.
+ * The two calls of a step share rows / n_rows / n_chunks / partials / snap and run in this order on one stream. */
+typedef struct FabindAdamRow {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    long long numel;
+    int chunk0, step_idx;
+    double lr, beta1, beta2, eps, weight_decay;
+    int decoupled, pad_;
+} FabindAdamRow;
+int fabind_adam_chunk(void);
+int fabind_multi_sqnorm(const FabindAdamRow* rows_dev, int n_rows, int n_chunks, const float* steps, float* partials, float* snap,
+                        hipStream_t stream);
+int fabind_multi_adam(const FabindAdamRow* rows_dev, int n_rows, int n_chunks, const float* partials, const float* snap, float* steps,
+                      float max_norm, int flags, float* grad_norm, int* skipped, hipStream_t stream);
 /* (round 6: src_dt = 2 = an fp32 source whose LO plane is packed, bf16(w - bf16(w)): with src_dt = 0 of the same source the hi | lo
  * fragment packs of the split-precision kernels.)
  * Many [N, K] weights (fp32 or bf16; element (n, k) at src[n * src_sr + k * src_sc], so a transposed source is a stride swap) into the

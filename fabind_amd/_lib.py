@@ -15,6 +15,8 @@ LIB_PATH = _cfg.knob("FABIND_LIB") or os.path.join(_HERE, "libfabind_hip.so")   
 ABI_VERSION = 19         # FABIND_ABI_VERSION of include/fabind_hip.h this binding mirrors
 DT_F32, DT_BF16 = 0, 1
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_SIGMOID, ACT_STORED_DERIV = 0, 1, 2, 3, 4
+# FB_GEMM_FAM_*: the kernel family fabind_gemm_plan reports
+GEMM_FAM_NT_F32, GEMM_FAM_NT_F32_BF16, GEMM_FAM_NT_BF16, GEMM_FAM_GLDS, GEMM_FAM_PIPE, GEMM_FAM_X3, GEMM_FAM_X3_PRO, GEMM_FAM_PERSIST = range(8)
 
 _vp, _i, _f, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
 
@@ -67,6 +69,7 @@ class AdamRow(ctypes.Structure):
 # name -> argtypes (every function returns int and takes the stream last)
 SIGNATURES = {
     "fabind_gemm": [ctypes.POINTER(GemmArgs), _vp],
+    "fabind_gemm_plan": [ctypes.POINTER(GemmArgs), ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)],   # launches nothing, takes no stream
     "fabind_gemm_tn_multi": [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp],
     "fabind_gemm_tn": [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp],
     "fabind_transpose_act": [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _vp],

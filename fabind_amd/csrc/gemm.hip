@@ -1523,12 +1523,14 @@ __global__ __launch_bounds__(WM * 128, MINW) void gemm_x3_kernel(FabindGemmArgs 
         for (int i = 0; i < NB4; ++i) rb[i] = *(const float4*)(wrow[i] + (inside ? gk : min(lc, K - 4)));
     };
     const bool tile_inside = (m0 + BM_ <= M) && (n0 + BN <= N) && (K % BK == 0);      // uniform: no element of any k-tile needs zeroing
-    auto put4 = [&](bf16_t* hi, bf16_t* lo, int o, float4 x, bool ok) {
-        if (PRO || !tile_inside) {
+    // (is_a: the prologue activation belongs to the A rows only -- the first PRO form ran it over the W rows of the stage as well,
+    //  act_pro(A) act_pro(W)^T, which nothing noticed because no caller of the split-bf16 kernel passes act_pro: tests/test_gpu_gemm_forms.py)
+    auto put4 = [&](bf16_t* hi, bf16_t* lo, int o, float4 x, bool ok, const bool is_a) {
+        if ((PRO && is_a) || !tile_inside) {
             float v[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                if constexpr (PRO) v[q] = apply_act(v[q], p.act_pro);
+                if (PRO && is_a) v[q] = apply_act(v[q], p.act_pro);
                 v[q] = ok ? v[q] : 0.f;
             }
             x = make_float4(v[0], v[1], v[2], v[3]);
@@ -1544,9 +1546,9 @@ __global__ __launch_bounds__(WM * 128, MINW) void gemm_x3_kernel(FabindGemmArgs 
         bf16_t* lo = hi + PLANE;
         const bool kok = tile_inside || k0 + lc < K;
 #pragma unroll
-        for (int i = 0; i < NA4; ++i) put4(hi, lo, (lr + (NT / 8) * i) * LS + lc, ra[i], kok && aok[i]);
+        for (int i = 0; i < NA4; ++i) put4(hi, lo, (lr + (NT / 8) * i) * LS + lc, ra[i], kok && aok[i], true);
 #pragma unroll
-        for (int i = 0; i < NB4; ++i) put4(hi, lo, (BM_ + lr + (NT / 8) * i) * LS + lc, rb[i], kok && wok[i]);
+        for (int i = 0; i < NB4; ++i) put4(hi, lo, (BM_ + lr + (NT / 8) * i) * LS + lc, rb[i], kok && wok[i], false);
     };
     const int fr = lane & 15, fk = (lane >> 4) * 8;
     auto compute = [&](int st) {
@@ -1627,8 +1629,14 @@ static int launch_x3(const FabindGemmArgs& p, int maxM, int maxN, hipStream_t st
     return 0;
 }
 
-extern "C" int fabind_gemm(const FabindGemmArgs* args, hipStream_t stream) {
-    FabindGemmArgs p = *args;
+// The selection half of fabind_gemm: validates the arguments, normalises them in place (K1, the accumulate -> residual rewrite, r_dtype,
+// epi_fast) and names the kernel that runs them: the family (FB_GEMM_FAM_* of fabind_hip.h; -1: an empty problem, nothing is launched)
+// and its configuration -- for the pipelined bf16 kernel the tile configuration AFTER the split-K and small-M switches, for the
+// split-bf16 kernel its tile height in units of 64 rows, 0 elsewhere.  It launches nothing.  fabind_gemm launches what this names and
+// fabind_gemm_plan reports it, so the two cannot drift.
+static int gemm_plan(FabindGemmArgs& p, int* family, int* cfg_out) {
+    *family = -1;
+    *cfg_out = 0;
     FB_REQUIRE(p.groups_ext || p.K % 8 == 0, "fabind_gemm: K must be a multiple of 8");
     FB_REQUIRE(p.A2 == nullptr || (p.K1 % BK == 0), "fabind_gemm: K1 must be a multiple of 32 when A2 is given");
     if (p.A2 == nullptr) p.K1 = p.K;
@@ -1695,9 +1703,8 @@ extern "C" int fabind_gemm(const FabindGemmArgs* args, hipStream_t stream) {
     FB_REQUIRE(p.C16 == nullptr || (p.C != nullptr && p.c_dtype == FB_DT_F32 && !p.groups && p.k_splits <= 1 && !p.store_preact &&
                                     p.ldc16 % 4 == 0 && ((uintptr_t)p.C16 & 7) == 0),
                "fabind_gemm: C16 (bf16 copy of C) needs a plain fp32 C (no groups / split-K / stored pre-activation), ldc16 % 4 == 0");
-    int maxM = p.groups ? p.max_m : p.M, maxN = p.groups ? p.max_n : p.N;
+    const int maxM = p.groups ? p.max_m : p.M, maxN = p.groups ? p.max_n : p.N;
     if (maxM <= 0 || maxN <= 0) return 0;
-    dim3 grid((maxN + BN - 1) / BN, (maxM + BM - 1) / BM, p.groups ? p.n_groups : (p.k_splits > 1 ? p.k_splits : 1));
     if (p.k_splits > 1) {
         FB_REQUIRE(!p.groups && p.c_dtype == FB_DT_F32 && !p.bias && !p.R && !p.dotvec && !p.aux && !p.accumulate &&
                        p.act_epi == FB_ACT_NONE && p.A2 == nullptr,
@@ -1709,43 +1716,85 @@ extern "C" int fabind_gemm(const FabindGemmArgs* args, hipStream_t stream) {
         FB_REQUIRE(((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.W % 16 == 0) && (p.A2 == nullptr || ((uintptr_t)p.A2 % 16 == 0 && p.lda2 % 4 == 0)),
                    "fabind_gemm: split-bf16 operands must be 16-byte aligned");
         FB_REQUIRE(p.lda % 4 == 0 && p.ldw % 4 == 0, "fabind_gemm: split-bf16 operands are read as 16-byte rows (lda % 4 == 0, ldw % 4 == 0)");
-        if (p.act_pro != FB_ACT_NONE) launch_x3<2, 2, true>(p, maxM, maxN, stream);
-        else if (g_x3_wm == 4) launch_x3<4, 2, false>(p, maxM, maxN, stream);
-        else launch_x3<2, 2, false>(p, maxM, maxN, stream);
+        if (p.act_pro != FB_ACT_NONE) { *family = FB_GEMM_FAM_X3_PRO; *cfg_out = 2; }
+        else { *family = FB_GEMM_FAM_X3; *cfg_out = (g_x3_wm == 4) ? 4 : 2; }
     } else if (p.w_dtype == FB_DT_F32) {
         FB_REQUIRE(p.a_dtype == FB_DT_F32, "fabind_gemm: fp32 MMA needs fp32 A");
-        hipLaunchKernelGGL((gemm_nt_kernel<float, float>), grid, dim3(256), 0, stream, p);
+        *family = FB_GEMM_FAM_NT_F32;
     } else if (p.a_dtype == FB_DT_F32) {
-        hipLaunchKernelGGL((gemm_nt_kernel<float, bf16_t>), grid, dim3(256), 0, stream, p);
+        *family = FB_GEMM_FAM_NT_F32_BF16;
     } else if (!p.groups_ext && p.act_pro == FB_ACT_NONE && p.K % FBK == 0 && p.lda % 8 == 0 && p.ldw % 8 == 0 &&
                ((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.W % 16 == 0) &&
                (p.A2 == nullptr || (g_gemm_cfg != 0 && p.K1 % FBK == 0 && p.lda2 % 8 == 0 && ((uintptr_t)p.A2 % 16 == 0)))) {
         const long n_tiles = (long)((maxM + 255) / 256) * ((maxN + BN - 1) / BN);
         if (g_gemm_persist && !p.groups && p.k_splits <= 1 && n_tiles >= 2048 && p.K <= 2048) {
-            launch_persist<4, 32, 3>(p, stream);
-            FB_CHECK_LAUNCH();
-            return 0;
-        }
-        int cfg = (p.k_splits > 1 && g_gemm_cfg == 0) ? 3 : g_gemm_cfg;
-        int row_tile0 = 0;
-        /* few row tiles (ligand rows, pocket-sized batches): the 256-row tile leaves most CUs idle -- 128-row tiles double the work-group
-           count; same k-order, bitwise-equal results (tools/probes/gemm_small_m.py) */
-        if (cfg == 13 && !p.groups && g_gemm_small_m && n_tiles * (p.k_splits > 1 ? p.k_splits : 1) < g_gemm_small_m) cfg = 6;
-        switch (cfg) {
-            case 1: launch_pipe<2, 32, 4>(p, maxM, maxN, stream); break;
-            case 2: launch_pipe<2, 64, 3>(p, maxM, maxN, stream); break;
-            case 3: launch_pipe<4, 32, 3>(p, maxM, maxN, stream); break;
-            case 4: launch_pipe<4, 64, 3>(p, maxM, maxN, stream); break;
-            case 5: launch_pipe<4, 32, 4>(p, maxM, maxN, stream); break;
-            case 6: launch_pipe<2, 32, 3>(p, maxM, maxN, stream); break;
-            case 7: launch_pipe<4, 32, 2>(p, maxM, maxN, stream); break;
-            case 8: launch_pipe<2, 32, 2>(p, maxM, maxN, stream); break;
-            case 9: launch_pipe<4, 64, 2>(p, maxM, maxN, stream); break;
-            case 13: launch_pipe<4, 32, 3, 4>(p, maxM, maxN, stream, row_tile0); break;   /* cfg 3 under a 4-waves-per-SIMD bound (default) */
-            default: hipLaunchKernelGGL(gemm_bf16_glds_kernel, grid, dim3(256), 0, stream, p);
+            *family = FB_GEMM_FAM_PERSIST;
+        } else {
+            int cfg = (p.k_splits > 1 && g_gemm_cfg == 0) ? 3 : g_gemm_cfg;
+            /* few row tiles (ligand rows, pocket-sized batches): the 256-row tile leaves most CUs idle -- 128-row tiles double the work-group
+               count; same k-order, bitwise-equal results (tools/probes/gemm_small_m.py) */
+            if (cfg == 13 && !p.groups && g_gemm_small_m && n_tiles * (p.k_splits > 1 ? p.k_splits : 1) < g_gemm_small_m) cfg = 6;
+            const bool pipe = (cfg >= 1 && cfg <= 9) || cfg == 13;       /* every other value: the two-buffer LDS-DMA kernel */
+            *family = pipe ? FB_GEMM_FAM_PIPE : FB_GEMM_FAM_GLDS;
+            *cfg_out = pipe ? cfg : 0;
         }
     } else {
-        hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, stream, p);
+        *family = FB_GEMM_FAM_NT_BF16;
+    }
+    /* the LayerNorm fold lives in the fast epilogues 12 / 13 only, and only the pipelined kernels dispatch to those: a bf16 A the
+       LDS-DMA cannot take (a base that is not 16-byte aligned) or fabind_gemm_set_config(0) used to run the generic epilogue, which
+       ignores row_mu / row_rs / col_c -- an un-normalised result without an error */
+    if (foldq && *family != FB_GEMM_FAM_PIPE && *family != FB_GEMM_FAM_PERSIST) {
+        *family = -1;
+        FB_REQUIRE(false, "fabind_gemm: the row_mu / row_rs fold needs the pipelined bf16 kernel (16-byte aligned A / W, lda % 8 == 0, "
+                          "ldw % 8 == 0, fabind_gemm_set_config != 0)");
+    }
+    return 0;
+}
+
+extern "C" int fabind_gemm_plan(const FabindGemmArgs* args, int* family, int* epi_fast, int* cfg) {
+    FabindGemmArgs p = *args;
+    int fam = -1, c = 0;
+    const int rc = gemm_plan(p, &fam, &c);
+    if (family) *family = fam;
+    if (epi_fast) *epi_fast = p.epi_fast;
+    if (cfg) *cfg = c;
+    return rc;
+}
+
+extern "C" int fabind_gemm(const FabindGemmArgs* args, hipStream_t stream) {
+    FabindGemmArgs p = *args;
+    int family = -1, cfg = 0;
+    if (gemm_plan(p, &family, &cfg) != 0) return -1;
+    if (family < 0) return 0;
+    const int maxM = p.groups ? p.max_m : p.M, maxN = p.groups ? p.max_n : p.N;
+    const dim3 grid((maxN + BN - 1) / BN, (maxM + BM - 1) / BM, p.groups ? p.n_groups : (p.k_splits > 1 ? p.k_splits : 1));
+    switch (family) {
+        case FB_GEMM_FAM_X3_PRO: launch_x3<2, 2, true>(p, maxM, maxN, stream); break;
+        case FB_GEMM_FAM_X3:
+            if (cfg == 4) launch_x3<4, 2, false>(p, maxM, maxN, stream);
+            else launch_x3<2, 2, false>(p, maxM, maxN, stream);
+            break;
+        case FB_GEMM_FAM_NT_F32: hipLaunchKernelGGL((gemm_nt_kernel<float, float>), grid, dim3(256), 0, stream, p); break;
+        case FB_GEMM_FAM_NT_F32_BF16: hipLaunchKernelGGL((gemm_nt_kernel<float, bf16_t>), grid, dim3(256), 0, stream, p); break;
+        case FB_GEMM_FAM_NT_BF16: hipLaunchKernelGGL((gemm_nt_kernel<bf16_t, bf16_t>), grid, dim3(256), 0, stream, p); break;
+        case FB_GEMM_FAM_GLDS: hipLaunchKernelGGL(gemm_bf16_glds_kernel, grid, dim3(256), 0, stream, p); break;
+        case FB_GEMM_FAM_PERSIST: launch_persist<4, 32, 3>(p, stream); break;
+        case FB_GEMM_FAM_PIPE:
+            switch (cfg) {
+                case 1: launch_pipe<2, 32, 4>(p, maxM, maxN, stream); break;
+                case 2: launch_pipe<2, 64, 3>(p, maxM, maxN, stream); break;
+                case 3: launch_pipe<4, 32, 3>(p, maxM, maxN, stream); break;
+                case 4: launch_pipe<4, 64, 3>(p, maxM, maxN, stream); break;
+                case 5: launch_pipe<4, 32, 4>(p, maxM, maxN, stream); break;
+                case 6: launch_pipe<2, 32, 3>(p, maxM, maxN, stream); break;
+                case 7: launch_pipe<4, 32, 2>(p, maxM, maxN, stream); break;
+                case 8: launch_pipe<2, 32, 2>(p, maxM, maxN, stream); break;
+                case 9: launch_pipe<4, 64, 2>(p, maxM, maxN, stream); break;
+                default: launch_pipe<4, 32, 3, 4>(p, maxM, maxN, stream, 0); break;   /* 13: cfg 3 under a 4-waves-per-SIMD bound (default) */
+            }
+            break;
+        default: break;
     }
     FB_CHECK_LAUNCH();
     return 0;

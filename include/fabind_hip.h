@@ -72,7 +72,8 @@ const char* fabind_last_error(void);
  *     clamp decision is the forward's own (it used to be inferred from x_out - x, which fp32 rounding falsifies).
  *     Backward-compatible additions under 19: fabind_multi_sqnorm / fabind_multi_adam + FabindAdamRow, fabind_adam_chunk (the fused Adam / AdamW
  *     step with global-norm clip and non-finite skip; fabind_sizeof_args(5) = sizeof(FabindAdamRow)).  Purely additive: no existing entry
- *     point or struct changed, so the version stays.
+ *     point or struct changed, so the version stays.  Likewise fabind_gemm_plan + FB_GEMM_FAM_* (which kernel and epilogue fabind_gemm
+ *     selects, reported without a launch).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -139,6 +140,24 @@ typedef struct FabindGemmArgs {
 } FabindGemmArgs;
 
 int fabind_gemm(const FabindGemmArgs* args, hipStream_t stream);
+
+/* Which kernel fabind_gemm would run for `args` under the current development knobs, without launching anything: the same host
+ * function fabind_gemm itself dispatches through (same argument checks, same return code).
+ *   family:   FB_GEMM_FAM_* below; -1 for an empty problem (nothing is launched)
+ *   epi_fast: the specialised epilogue the launch asks for (0 = generic, 1-16, 20-25).  The nt and glds kernels always run the
+ *             generic epilogue; forms 20-25 fall back to it inside the kernel when N, ldc or an address rules out 16-byte accesses
+ *   cfg:      FB_GEMM_FAM_PIPE: the tile configuration after the split-K and small-M switches (fabind_gemm_set_config /
+ *             fabind_gemm_set_small_m); FB_GEMM_FAM_X3 / _X3_PRO: the tile height in units of 64 rows; 0 elsewhere
+ * Any of the three pointers may be NULL. */
+#define FB_GEMM_FAM_NT_F32 0      /* gemm_nt_kernel<float, float>: fp32 A, fp32 W, exact fp32 MFMA */
+#define FB_GEMM_FAM_NT_F32_BF16 1 /* gemm_nt_kernel<float, bf16>: fp32 A rounded to bf16 while staged */
+#define FB_GEMM_FAM_NT_BF16 2     /* gemm_nt_kernel<bf16, bf16>: bf16 operands the LDS-DMA kernels cannot take (K % 64, act_pro, alignment) */
+#define FB_GEMM_FAM_GLDS 3        /* gemm_bf16_glds_kernel: two-buffer LDS-DMA (fabind_gemm_set_config(0)) */
+#define FB_GEMM_FAM_PIPE 4        /* gemm_bf16_pipe_kernel: the pipelined LDS-DMA ring, configuration in cfg */
+#define FB_GEMM_FAM_X3 5          /* gemm_x3_kernel: split-bf16 contraction of fp32 operands */
+#define FB_GEMM_FAM_X3_PRO 6      /* gemm_x3_kernel with the prologue activation compiled in */
+#define FB_GEMM_FAM_PERSIST 7     /* gemm_bf16_persist_kernel (fabind_gemm_set_persistent; off by default) */
+int fabind_gemm_plan(const FabindGemmArgs* args, int* family, int* epi_fast, int* cfg);
 
 /* Weight-gradient contraction without transposes: C_part[s][m][n] = sum_{e in split s} Y[e,m] * X[e,n]
  * (bf16 row-major operands, fp32 partials [splits, M, N]; zero_page = >= 16 zero bytes in device memory).

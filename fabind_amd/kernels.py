@@ -9,7 +9,7 @@ from . import _lib
 from . import config as _cfg
 from ._lib import ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU, ACT_STORED_DERIV, GemmArgs, check, dt_code, ptr, stream
 
-__all__ = ["gemm", "transpose_act", "colsum", "edges_count", "edges_fill", "exclusive_scan", "inter_meta",
+__all__ = ["gemm", "colsum", "edges_count", "edges_fill", "exclusive_scan", "inter_meta",
            "edge_geom", "gcl_pre", "segment_sum", "coord_update", "cross_attn_fwd", "pair_bmat", "pair_hadamard",
            "inter_attn_fwd", "las_step", "select_rows", "ACT_NONE", "ACT_SILU", "ACT_RELU", "ACT_SIGMOID", "ACT_STORED_DERIV"]
 
@@ -128,14 +128,6 @@ def gemm(A, W, bias=None, A2=None, act_pro=ACT_NONE, act_epi=ACT_NONE, residual=
     _profiled(label, 2.0 * M * N * K if flops is None else float(flops),
               lambda: check(lib.fabind_gemm(ctypes.byref(a), stream()), "fabind_gemm"), nb)
     return (out if want_out else None), dot_out
-
-
-def transpose_act(x, act=ACT_NONE, out_dtype=None):
-    R, C = x.shape
-    out = torch.empty((C, R), dtype=out_dtype or x.dtype, device=x.device)
-    check(_lib.load().fabind_transpose_act(ptr(x), dt_code(x.dtype), _ld(x), ptr(out), dt_code(out.dtype), R, R, C, act,
-                                           stream()), "fabind_transpose_act")
-    return out
 
 
 def colsum(x, out=None, accumulate=False):

@@ -14,20 +14,18 @@ from ._lib import GemmArgs, check, dt_code, load, ptr, stream
 
 
 def act_dtype():
-    """Storage type of the large edge-/pair-level intermediates."""
+    """Storage type of the large edge-/pair-level intermediates, and of the GEMM operands."""
     return torch.float32 if _cfg.fp32_storage() else torch.bfloat16
 
 
-def mm_dtype():
-    return torch.float32 if _cfg.fp32_storage() else torch.bfloat16
-
-
-def _needs_grad(*ts):
-    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts)
+mm_dtype = act_dtype
 
 
 def needs_grad(*ts):
-    return _needs_grad(*ts)
+    return torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in ts)
+
+
+_needs_grad = needs_grad
 
 
 def _nchunk(rows):
@@ -41,14 +39,13 @@ def _ksplit(R):
     return S, (R + unit - 1) // unit * unit
 
 
-def _transposed(x, act=K.ACT_NONE, Rp=None):
-    """act(x)^T as an mm-dtype [C, Rp] matrix (zero padded) for K=R contractions."""
+def _transposed(x, Rp):
+    """x^T as an mm-dtype [C, Rp] matrix (zero padded) for K=R contractions."""
     R, C = x.shape
-    Rp = Rp or _ksplit(R)[1]
     out = torch.empty((C, Rp), dtype=mm_dtype(), device=x.device)
     if Rp != R:
         out[:, R:].zero_()
-    check(load().fabind_transpose_act(ptr(x), dt_code(x.dtype), x.stride(0), ptr(out), dt_code(out.dtype), Rp, R, C, act,
+    check(load().fabind_transpose_act(ptr(x), dt_code(x.dtype), x.stride(0), ptr(out), dt_code(out.dtype), Rp, R, C, K.ACT_NONE,
                                       stream()), "fabind_transpose_act")
     return out
 
@@ -63,44 +60,6 @@ def _tn_ok(dpre, x, x2):
             and dpre.stride(0) % 8 == 0 and x.stride(0) % 8 == 0 and dpre.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0)
 
 
-def _tn_queue(dpre, x, x2, out_dtype, want_db, W):
-    """The TN contraction(s) of one weight gradient put on the queue of kernels.tn_flush (bf16 operands) -> (dW, db) whose contents
-    become valid at the flush; None when the contraction is not one for the queue (large operands, no backward pass running, ...)."""
-    if W is None or not K.tn_can_queue(dpre, x if x2 is None or x.numel() >= x2.numel() else x2, W.data_ptr()):
-        return None
-    M, K1, K2 = dpre.shape[1], x.shape[1], (x2.shape[1] if x2 is not None else 0)
-    dW = torch.empty((M, K1 + K2), dtype=out_dtype, device=dpre.device)
-    db = torch.empty(M, dtype=torch.float32, device=dpre.device) if want_db else None
-    K.gemm_tn_queued(dpre, x, dW[:, :K1] if K2 else dW, db, key=W.data_ptr())
-    if K2:
-        K.gemm_tn_queued(dpre, x2, dW[:, K1:], None, key=W.data_ptr())
-    return dW, db
-
-
-def _weight_grad(dpre, x, act_pro, x2=None, out_dtype=torch.float32, want_db=False, W=None):
-    """dW = dpre^T [act(x) | x2] as out_dtype.  bf16: TN contraction with LDS transpose reads (no transposed copies), its split
-    reduction writing out_dtype directly; fp32 parity mode / odd widths: explicit transposes + split-K NT GEMMs over the (padded)
-    row dimension.  want_db: -> (dW, db) with db = dpre^T 1 (fp32) -- from the SAME contraction launches when the TN path runs
-    (`fabind_gemm_tn(..., with_colsum)`; the split reduction writes dW as out_dtype and db as fp32), a separate column sum otherwise.
-    W: the weight this is the gradient of (a tensor `kernels.tn_hook` was called on in forward): contractions that do not fill the chip
-    alone are queued and run with the rest of the backward pass's weight gradients as one launch (kernels.tn_flush)."""
-    if not want_db:
-        return _weight_grad_f32(dpre, x, act_pro, x2, out_dtype, W)
-    if FUSE_DB_TN and act_pro == K.ACT_NONE and _x3_tn_ok(dpre, x, x2) and dpre.shape[1] % 4 == 0:
-        return _x3_weight_grad(dpre, x, x2, out_dtype, True, W)
-    if FUSE_DB_TN and act_pro == K.ACT_NONE and _tn_ok(dpre, x, x2):
-        q = _tn_queue(dpre, x, x2, out_dtype, True, W)
-        if q is not None:
-            return q
-        dW, db = K.gemm_tn(dpre, x, out_dtype=out_dtype, with_colsum=True)
-        if x2 is not None:
-            dW = torch.cat([dW, K.gemm_tn(dpre, x2, out_dtype=out_dtype)], 1)
-        return dW, db
-    return _weight_grad_f32(dpre, x, act_pro, x2, out_dtype, W), K.colsum(dpre)
-
-
-
-
 def _x3_tn_ok(dpre, x, x2):
     """'bf16x3' mode: the weight-gradient contraction dW = dpre^T x runs on bf16 ROUNDINGS of its two fp32 operands through the
     TN kernel (fp32 accumulation over the rows; no transposed copies).  Every weight-gradient entry is a sum over 1e5 .. 1e6 rows
@@ -113,8 +72,10 @@ def _x3_tn_ok(dpre, x, x2):
             and dpre.shape[1] % 8 == 0 and x.shape[1] % 8 == 0 and (x2 is None or x2.shape[1] % 8 == 0) and dpre.shape[0] >= 256)
 
 
-def _b16_copy(x):
-    """bf16 copy of an fp32 activation, remembered on the tensor (an epilogue may already have attached one: _attach_b16)."""
+def _b16(x):
+    """bf16 copy of an fp32 activation, remembered on the tensor (keyed on its version counter, so an in-place update invalidates
+    it; an epilogue may already have attached one: _attach_b16): a residual-stream tensor feeds two or three Linears per layer,
+    and each of them used to cast it again."""
     if x.dtype == torch.bfloat16:
         return x
     c = getattr(x, "_fab_b16", None)
@@ -129,43 +90,70 @@ def _b16_copy(x):
     return y
 
 
-def _x3_weight_grad(dpre, x, x2, out_dtype, want_db, W=None):
-    """-> (dW, db or None): the 'bf16x3' weight gradient on bf16 roundings (see _x3_tn_ok); db rides along as the TN kernel's column sums."""
-    d16 = dpre.to(torch.bfloat16)
-    x16, x216 = _b16_copy(x), (_b16_copy(x2) if x2 is not None else None)
-    q = _tn_queue(d16, x16, x216, out_dtype, want_db, W)
-    if q is not None:
-        return q
-    if want_db:
-        dW, db = K.gemm_tn(d16, x16, out_dtype=out_dtype, with_colsum=True)
-    else:
-        dW, db = K.gemm_tn(d16, x16, out_dtype=out_dtype), None
-    if x2 is not None:
-        dW = torch.cat([dW, K.gemm_tn(d16, x216, out_dtype=out_dtype)], 1)
+def _tn(dpre, x, x2, W, with_db):
+    """(dW as W.dtype, db or None) = (dpre^T [x | x2], dpre^T 1) of bf16 operands by the TN kernel: LDS transpose reads (no transposed
+    copies), its split reduction writing W.dtype directly and, with_db, the column sums as fp32 from the SAME launches.  W is a tensor
+    `kernels.tn_hook` was called on in forward: a contraction that does not fill the chip alone is queued and runs with the rest of the
+    backward pass's weight gradients as one launch (kernels.tn_flush) -- its results become valid at the flush."""
+    M, K1, K2 = dpre.shape[1], x.shape[1], (x2.shape[1] if x2 is not None else 0)
+    if K.tn_can_queue(dpre, x if x2 is None or x.numel() >= x2.numel() else x2, W.data_ptr()):
+        dW = torch.empty((M, K1 + K2), dtype=W.dtype, device=dpre.device)
+        db = torch.empty(M, dtype=torch.float32, device=dpre.device) if with_db else None
+        K.gemm_tn_queued(dpre, x, dW[:, :K1] if K2 else dW, db, key=W.data_ptr())
+        if K2:
+            K.gemm_tn_queued(dpre, x2, dW[:, K1:], None, key=W.data_ptr())
+        return dW, db
+    dW, db = K.gemm_tn(dpre, x, out_dtype=W.dtype, with_colsum=True) if with_db else (K.gemm_tn(dpre, x, out_dtype=W.dtype), None)
+    if K2:
+        dW = torch.cat([dW, K.gemm_tn(dpre, x2, out_dtype=W.dtype)], 1)
     return dW, db
 
 
-def _weight_grad_f32(dpre, x, act_pro, x2, out_dtype, W=None):
-    if act_pro == K.ACT_NONE and _x3_tn_ok(dpre, x, x2):
-        return _x3_weight_grad(dpre, x, x2, out_dtype, False, W)[0]
-    if act_pro == K.ACT_NONE and _tn_ok(dpre, x, x2):
-        q = _tn_queue(dpre, x, x2, out_dtype, False, W)
-        if q is not None:
-            return q[0]
-        if x2 is None:
-            return K.gemm_tn(dpre, x, out_dtype=out_dtype)
-        return torch.cat([K.gemm_tn(dpre, x, out_dtype=out_dtype), K.gemm_tn(dpre, x2, out_dtype=out_dtype)], 1)
-    if out_dtype != torch.float32:
-        return _weight_grad_f32(dpre, x, act_pro, x2, torch.float32).to(out_dtype)
-    S, Rp = _ksplit(dpre.shape[0])
-    dpt = _transposed(dpre, Rp=Rp)
-    xt = _transposed(x, act_pro, Rp=Rp)
-    if x2 is not None:
-        xt = torch.cat([xt, _transposed(x2, Rp=Rp)], 0)
-    if S == 1:
-        return K.gemm(dpt, xt)[0]
-    part, _ = K.gemm(dpt, xt, k_splits=S)                                  # [S, N, K] fp32 partials
-    return K.colsum(part.reshape(S, -1)).reshape(part.shape[1], part.shape[2])
+def _wgrad_plan(dpre, x, x2, want_db):
+    """Which contraction computes dW = dpre^T [x | x2], and whether the bias gradient rides with it -> ("x3_tn" | "tn" | "nt", bool).
+    Reads dtypes, shapes, strides and alignment only (tests/test_host_cpu.py pins the table on CPU tensors)."""
+    if _x3_tn_ok(dpre, x, x2):
+        return "x3_tn", bool(want_db and FUSE_DB_TN and dpre.shape[1] % 4 == 0)
+    if _tn_ok(dpre, x, x2):
+        return "tn", bool(want_db and FUSE_DB_TN)
+    return "nt", False
+
+
+def _weight_grad(dpre, x, x2, W, want_db):
+    """-> (dW = dpre^T [x | x2] as W.dtype, db = dpre^T 1 as fp32 or None): the one weight-gradient ladder (_wgrad_plan).
+    'x3_tn': the TN kernel on bf16 roundings of fp32 operands (see _x3_tn_ok); 'tn': the TN kernel on the bf16 operands; 'nt' (fp32
+    parity mode, exact 'bf16x3' backward, odd widths): explicit transposes + split-K NT GEMMs over the (padded) row dimension,
+    accumulated in fp32 and never queued.  A bias gradient that did not ride with the contraction is a column sum of its own."""
+    path, with_db = _wgrad_plan(dpre, x, x2, want_db)
+    if path == "x3_tn":
+        dW, db = _tn(dpre.to(torch.bfloat16), _b16(x), _b16(x2) if x2 is not None else None, W, with_db)
+    elif path == "tn":
+        dW, db = _tn(dpre, x, x2, W, with_db)
+    else:
+        S, Rp = _ksplit(dpre.shape[0])
+        dpt, xt = _transposed(dpre, Rp), _transposed(x, Rp)
+        if x2 is not None:
+            xt = torch.cat([xt, _transposed(x2, Rp)], 0)
+        if S == 1:
+            dW = K.gemm(dpt, xt)[0]
+        else:
+            part, _ = K.gemm(dpt, xt, k_splits=S)                              # [S, N, K] fp32 partials
+            dW = K.colsum(part.reshape(S, -1)).reshape(part.shape[1], part.shape[2])
+        dW, db = dW.to(W.dtype), None
+    if want_db and db is None:
+        db = K.colsum(dpre)
+    return dW, db
+
+
+def _param_grads(dpre, x, x2, W, want_dW, want_db, db=None):
+    """(dW, db) of y = [x | x2] W^T + b from dpre = dL/dy; db: the bias gradient where the pass that made dpre already has it (_dpre)."""
+    dW = None
+    if want_dW:
+        dW, db_ = _weight_grad(dpre, x, x2, W, want_db and db is None)
+        db = db if db is not None else db_
+    elif want_db and db is None:
+        db = K.colsum(dpre)
+    return dW, (db if want_db else None)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -217,28 +205,71 @@ def _mul_dropmask_colsum(dy, p_drop, seed, out_dtype):
     return out, db
 
 
+def _dpre_plan(dy, act, drop, want_db, want_dW):
+    """Which pass over dy = dL/dy makes the pre-activation gradient, and does it carry the bias gradient -> ("dropmask" | "act" | "cast" |
+    "none", bool).  A pass is needed for a regenerated dropout mask, an activation adjoint or a dtype other than the contractions';
+    its column-partials form yields the bias gradient unless that rides with the queued weight-gradient contraction (_db_in_tn) or the
+    width is not the kernel's (C % 4).  The drop-mask pass exists in its column-sum form only.  Reads dtype and shape only
+    (tests/test_host_cpu.py pins the table)."""
+    if drop is not None:
+        return "dropmask", bool(want_db)
+    kind = "act" if act != K.ACT_NONE else "cast" if dy.dtype != mm_dtype() else "none"
+    return kind, bool(want_db and kind != "none" and dy.dim() == 2 and dy.shape[1] % 4 == 0 and not (want_dW and _db_in_tn(dy)))
+
+
+def _dpre(dy, act, aux, scale, drop, want_db, want_dW):
+    """-> (dpre = scale * dy * act'(aux) [or dy * keep / (1 - p) of the mask regenerated from drop = (p, seed)] in mm dtype, db or None);
+    aux: the saved output (ReLU) or the stored derivative (K.ACT_STORED_DERIV); scale: the 1 / (1 - p) of a ReLU output's dropout.
+    dpre is dy itself when no pass is needed; db is None when the pass does not carry it (_dpre_plan): _param_grads takes it from there."""
+    kind, with_db = _dpre_plan(dy, act, drop, want_db, want_dW)
+    md = mm_dtype()
+    if kind == "dropmask":
+        dpre, db = _mul_dropmask_colsum(dy, drop[0], drop[1], md)
+        return dpre, (db if with_db else None)
+    if kind == "none":
+        return dy, None
+    scale = scale if kind == "act" else 1.0
+    return _mul_dact_colsum(dy, aux, act, md, scale) if with_db else (_mul_dact(dy, aux, act, md, scale), None)
+
+
 def _mm_in(x):
-    """Operand as the GEMM wants it: bf16 copy of an fp32 activation in bf16 mode.  The copy is remembered on the tensor
-    (keyed on its version counter, so an in-place update invalidates it): a residual-stream tensor feeds two or three
-    Linears per layer, and each of them used to cast it again."""
-    if x is not None and _cfg.get_precision() == "bf16" and x.dtype == torch.float32:
-        c = getattr(x, "_fab_b16", None)
-        if c is not None and c[0] == x._version:
-            return c[1]
-        y = x.to(torch.bfloat16)
-        if x.dim() == 2 and x.is_contiguous():
-            try:
-                x._fab_b16 = (x._version, y)
-            except Exception:
-                pass
-        return y
-    return x
+    """Operand as the GEMM wants it: the bf16 copy (_b16) of an fp32 activation in bf16 mode."""
+    return _b16(x) if (x is not None and _cfg.get_precision() == "bf16" and x.dtype == torch.float32) else x
 
 
-def _wt(W):
-    """W^T as a contiguous operand: the copy the parameter pack wrote next to W (param_pack.ParamPack.cat(with_T=True)), else a transpose kernel."""
+def _stored_wt(W):
+    """Forward-time lookup of the W^T the parameter pack wrote next to W (param_pack.ParamPack.cat(with_T=True)), or None; kept on
+    ctx, because an attribute of a tensor is not something save_for_backward promises to hand back."""
     t = getattr(W, "_fab_T", None)
-    return t if (t is not None and t.shape == (W.shape[1], W.shape[0])) else W.t().contiguous()
+    return t if (t is not None and t.shape == (W.shape[1], W.shape[0])) else None
+
+
+def _wt(Wt, W):
+    """W^T as a contiguous [K, N] operand of the input-gradient GEMM: what forward found (_stored_wt), else a transpose kernel."""
+    return Wt if Wt is not None else W.t().contiguous()
+
+
+def _padded_k(dpre, W, Wt, Np):
+    """(dpre, W^T) as the operands of the input-gradient GEMM dpre W, its contraction dimension N = W.shape[0] zero-padded to Np columns
+    (the GEMM contracts multiples of 8); Np == N: dpre itself and the stored / transposed W^T (_wt)."""
+    N = W.shape[0]
+    if Np == N:
+        return dpre, _wt(Wt, W)
+    Wp = torch.zeros((W.shape[1], Np), dtype=W.dtype, device=W.device)
+    Wp[:, :N] = W.t()
+    dp = torch.zeros((dpre.shape[0], Np), dtype=dpre.dtype, device=dpre.device)
+    dp[:, :N] = dpre
+    return dp, Wp
+
+
+def _drop_scale(p_drop):
+    """1 / (1 - p) at the kernels' 16-bit threshold (keep = [hash & 0xffff >= round(p * 65536)])."""
+    return 1.0 / (1.0 - int(p_drop * 65536.0 + 0.5) / 65536.0)
+
+
+def _drop_seed(p_drop):
+    """Key of a counter-based dropout mask: one draw from torch's CPU generator (no device sync); none without dropout."""
+    return int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0.0 else 0
 
 
 def _attach_b16(y, y16):
@@ -266,8 +297,7 @@ class _Linear(torch.autograd.Function):
         assert p_drop == 0.0 or (act_epi == K.ACT_RELU and residual is None) or \
             (drop_regen and out_dtype == torch.float32 and x2 is None and W32 is None and W.shape[0] % 4 == 0), \
             "epilogue dropout under autograd: ReLU without a residual, or no activation with an fp32 output"
-        thr = int(p_drop * 65536.0 + 0.5)
-        ctx.drop_scale = 1.0 / (1.0 - thr / 65536.0)
+        ctx.drop_scale = _drop_scale(p_drop)
         ctx.drop_regen = (float(p_drop), int(seed)) if drop_regen else None
         xin, x2in = _mm_in(x), _mm_in(x2)
         D = None
@@ -282,13 +312,7 @@ class _Linear(torch.autograd.Function):
         if holder is not None:                        # the caller wants the epilogue to emit the bf16 operand copy of y as well
             y16 = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
             holder.append(y16)
-        if isinstance(W32, tuple):
-            _gemm_split_rows(x, xin, W, W32, b, y, y16)
-        elif W32 is not None:    # a split-precision site of the bf16 mode (config.set_split_sites): the forward contracts the fp32 activation with
-            #                      the fp32 master weight; what is saved -- and everything the backward does -- are the bf16 operands
-            K.gemm(x, W32, bias=b, A2=x2, act_epi=act_epi, residual=residual, out=y, out2=D, out16=y16, p_drop=p_drop, seed=seed, force_x3=True)
-        else:
-            K.gemm(xin, W, bias=b, A2=x2in, act_epi=act_epi, residual=residual, out=y, out2=D, out16=y16, p_drop=p_drop, seed=seed)
+        _linear_fwd(x, xin, x2, x2in, W, W32, b, y, act_epi=act_epi, residual=residual, D=D, y16=y16, p_drop=p_drop, seed=seed)
         ctx.act_epi, ctx.x_dtype = (K.ACT_SILU if relu_res else act_epi), x.dtype       # backward: stored derivative
         ctx.x2_dtype = x2.dtype if x2 is not None else None
         ctx.has_b, ctx.has_res, ctx.has_x2 = b is not None, residual is not None, x2 is not None
@@ -296,34 +320,19 @@ class _Linear(torch.autograd.Function):
         ctx.sink_x, ctx.sink_res = _sink_of(x), _sink_of(residual)
         ctx.x_shape = x.shape
         ctx.save_for_backward(xin, W, x2in, y if (act_epi == K.ACT_RELU and not relu_res) else None, D)
-        ctx.Wt = getattr(W, "_fab_T", None)           # W^T written by the parameter pack next to W, if any
+        ctx.Wt = _stored_wt(W)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, W, x2, y, D = ctx.saved_tensors
         dy = dy.contiguous()
-        md = mm_dtype()
-        db = None
-        want_db = ctx.has_b and ctx.needs_input_grad[2]
-        fuse_db = want_db and dy.dim() == 2 and dy.shape[1] % 4 == 0   # bias gradient in the same pass over dy
-        if fuse_db and ctx.needs_input_grad[1] and _db_in_tn(dy):
-            fuse_db = False                                                       # ... or with the queued weight-gradient contraction
-        md_op = _mul_dact_colsum if fuse_db else (lambda *a: (_mul_dact(*a), None))      # (dy, aux, act, out dtype[, scale])
-        if ctx.drop_regen is not None:
-            dpre, db = _mul_dropmask_colsum(dy, ctx.drop_regen[0], ctx.drop_regen[1], md)
-            if not want_db:
-                db = None
-        elif ctx.act_epi == K.ACT_RELU:
-            dpre, db = md_op(dy, y, K.ACT_RELU, md, ctx.drop_scale)
-        elif ctx.act_epi == K.ACT_SILU:
-            dpre, db = md_op(dy, D, K.ACT_STORED_DERIV, md)
-        elif dy.dtype != md:
-            dpre, db = md_op(dy, None, K.ACT_NONE, md)           # dtype conversion only
-        else:
-            dpre = dy
+        want_dW, want_db = ctx.needs_input_grad[1], ctx.has_b and ctx.needs_input_grad[2]
+        act = K.ACT_STORED_DERIV if ctx.act_epi == K.ACT_SILU else ctx.act_epi
+        aux = y if ctx.act_epi == K.ACT_RELU else D                       # the ReLU output's zeros, or the stored derivative
+        dpre, db = _dpre(dy, act, aux, ctx.drop_scale, ctx.drop_regen, want_db, want_dW)
         K1, N = x.shape[1], W.shape[0]
-        dx = dx2 = dW = None
+        dx = dx2 = None
         # x with a shared gradient buffer (ops.shared_grad): its input gradient is stored / accumulated there by the GEMM epilogue.
         # fp32 tensors (the v1 residual stream) and bf16 ones (the FABind+ pair embedding: next layer's residual deposit + this
         # Linear's gradient + the inter-edge row gather meet in ONE epilogue pass instead of two [pairs, H] adds)
@@ -333,14 +342,7 @@ class _Linear(torch.autograd.Function):
             # a multiple of 64 sends the input-gradient GEMM to the register-staged fallback kernel, which wrote the [M, K] gradient
             # at < 1 TB/s (756 us for 648 MB); zero-padded to 64 it runs on the LDS-DMA kernel with the row-contiguous epilogue
             pad64 = N % 64 != 0 and N <= 64 and dpre.shape[0] >= 65536 and dpre.dtype == torch.bfloat16
-            if N % 8 == 0 and not pad64:
-                Wt, dmm = (ctx.Wt if ctx.Wt is not None else W.t().contiguous()), dpre      # [K, N] (parameter-only transpose)
-            else:                                                       # tiny heads (N = 1): pad the contraction dim to 8
-                Np = 64 if pad64 else (N + 7) // 8 * 8
-                Wt = torch.zeros((W.shape[1], Np), dtype=W.dtype, device=W.device)
-                Wt[:, :N] = W.t()
-                dmm = torch.zeros((dpre.shape[0], Np), dtype=dpre.dtype, device=dpre.device)
-                dmm[:, :N] = dpre
+            dmm, Wt = _padded_k(dpre, W, ctx.Wt, 64 if pad64 else (N + 7) // 8 * 8)      # (tiny heads, N = 1: the contraction dim padded to 8)
             if sink_x is not None:
                 dx = sink_x.gemm_into(dmm, Wt[:K1], x, ctx.x_dtype)     # (x2, if any, gets its own GEMM over the other K-slice of W)
                 if ctx.has_x2 and ctx.needs_input_grad[3]:
@@ -353,12 +355,7 @@ class _Linear(torch.autograd.Function):
                         dx2 = dx2.to(ctx.x2_dtype)
                 else:
                     dx = dfull
-        if ctx.needs_input_grad[1] and want_db and db is None:
-            dW, db = _weight_grad(dpre, x, K.ACT_NONE, x2, W.dtype, want_db=True, W=W)
-        elif ctx.needs_input_grad[1]:
-            dW = _weight_grad(dpre, x, K.ACT_NONE, x2, W.dtype, W=W)
-        if want_db and db is None:
-            db = K.colsum(dpre)
+        dW, db = _param_grads(dpre, x, x2, W, want_dW, want_db, db)
         dres = None
         if ctx.has_res and ctx.needs_input_grad[4]:
             dres = dy if dy.dtype == ctx.res_dtype else dy.to(ctx.res_dtype)      # (a bf16 residual stream takes dy as it is)
@@ -377,6 +374,19 @@ def _gemm_split_rows(x, xin, W, W32, b, y, y16):
         if b_ > a_:
             K.gemm(xin, W[a_:b_], bias=b[a_:b_] if b is not None else None, out=y[:, a_:b_], out16=y16[:, a_:b_] if y16 is not None else None)
     K.gemm(x, W32p, bias=b[lo:hi] if b is not None else None, out=y[:, lo:hi], out16=y16[:, lo:hi] if y16 is not None else None, force_x3=True)
+
+
+def _linear_fwd(x, xin, x2, x2in, W, W32, b, y, act_pro=K.ACT_NONE, act_epi=K.ACT_NONE, residual=None, D=None, y16=None, p_drop=0.0, seed=0):
+    """The forward launch(es) of a Linear into y (D: the stored derivative, y16: the bf16 operand copy of y); xin / x2in = _mm_in(x / x2).
+    W32 a (W32p, lo, hi) tuple: _gemm_split_rows.  W32 a tensor: a split-precision site of the bf16 mode (config.set_split_sites) -- the
+    forward contracts the fp32 activation with the fp32 master weight; what is saved -- and everything the backward does -- are the bf16
+    operands.  Else the plain GEMM on the mode's operands."""
+    if isinstance(W32, tuple):
+        _gemm_split_rows(x, xin, W, W32, b, y, y16)
+    elif W32 is not None:
+        K.gemm(x, W32, bias=b, A2=x2, act_epi=act_epi, residual=residual, out=y, out2=D, out16=y16, p_drop=p_drop, seed=seed, force_x3=True)
+    else:
+        K.gemm(xin, W, bias=b, A2=x2in, act_pro=act_pro, act_epi=act_epi, residual=residual, out=y, out2=D, out16=y16, p_drop=p_drop, seed=seed)
 
 
 def _split_site_ok(x, W, W32, x2, act_pro, out_dtype, p_drop, act_epi=K.ACT_NONE, residual=None):
@@ -400,7 +410,7 @@ def linear(x, W, b=None, act_pro=K.ACT_NONE, act_epi=K.ACT_NONE, residual=None, 
     split-precision site, config.set_split_sites); the backward is the bf16 one either way."""
     if x.stride(-1) != 1:
         x = x.contiguous()
-    seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0.0 else 0
+    seed = _drop_seed(p_drop)
     if not _split_site_ok(x, W, W32, x2, act_pro, out_dtype, p_drop, act_epi, residual):
         W32 = None
     if _needs_grad(x, W, b, x2, residual):
@@ -412,15 +422,9 @@ def linear(x, W, b=None, act_pro=K.ACT_NONE, act_epi=K.ACT_NONE, residual=None, 
     y16 = None
     if _want16(out_dtype, act_epi, want16) and act_pro == K.ACT_NONE and (p_drop == 0.0 or (act_epi == K.ACT_NONE and x2 is None and W.shape[0] % 4 == 0)):
         y16 = torch.empty((x.shape[0], W.shape[0]), dtype=torch.bfloat16, device=x.device)      # (with epilogue dropout: the plain fp32 epilogues only)
-    if isinstance(W32, tuple):
-        y = torch.empty((x.shape[0], W.shape[0]), dtype=out_dtype, device=x.device)
-        _gemm_split_rows(x, _mm_in(x), W, W32, b, y, y16)
-        return _attach_b16(y, y16)
-    if W32 is not None:
-        y, _ = K.gemm(x, W32, bias=b, A2=x2, act_epi=act_epi, residual=residual, out_dtype=out_dtype, out16=y16, force_x3=True)
-        return _attach_b16(y, y16)
-    y, _ = K.gemm(_mm_in(x), W, bias=b, A2=_mm_in(x2), act_pro=act_pro, act_epi=act_epi, residual=residual,
-                  out_dtype=out_dtype, p_drop=p_drop, seed=seed, out16=y16)
+    y = torch.empty((x.shape[0], W.shape[0]), dtype=out_dtype, device=x.device)
+    xin, x2in = (_mm_in(x), _mm_in(x2)) if (W32 is None or isinstance(W32, tuple)) else (None, None)    # (a whole split site reads fp32 only)
+    _linear_fwd(x, xin, x2, x2in, W, W32, b, y, act_pro, act_epi, residual, y16=y16, p_drop=p_drop, seed=seed)
     return _attach_b16(y, y16)
 
 
@@ -441,76 +445,51 @@ class _MLP2(torch.autograd.Function):
         xin, x2in = _mm_in(x), _mm_in(x2)
         M, N1 = x.shape[0], W1.shape[0]
         ad = act_dtype()
-        y16 = None
         split_ok = W32 is not None and ctx.drop is None and _split_site_ok(x, W1, W32[0], x2, K.ACT_NONE, torch.float32, 0.0, act, None)
         if split_ok and chain is not None and _chain_ok(x, x2, residual, W1, W2):
             # round 6: the whole forward of the MLP as ONE split-precision kernel (csrc/node_chain.hip): the fp32 hidden layer never leaves the
             # CU; what the (unchanged, bf16) backward needs -- bf16(hidden) and, for SiLU, bf16 of its derivative -- is written on the way
             y, y16, t, D = K.node_chain_x3_fwd(x, x2, chain, b1.float(), b2.float(), act, 0 if x2 is not None else 1, residual=residual,
                                                want16=holder is not None, save=True)
-            if holder is not None:
-                holder.append(y16)
-            ctx.act, ctx.has_x2, ctx.has_res = act, x2 is not None, residual is not None
-            ctx.res_is_x = residual is x
-            ctx.sink_x, ctx.sink_res = _sink_of(x), _sink_of(residual)
-            ctx.x2_dtype = x2.dtype if x2 is not None else None
-            ctx.save_for_backward(xin, x2in, W1, W2, t, D)
-            ctx.W1t, ctx.W2t = getattr(W1, "_fab_T", None), getattr(W2, "_fab_T", None)
-            return y
-        if holder is not None:
-            y16 = torch.empty((M, W2.shape[0]), dtype=torch.bfloat16, device=x.device)
-            holder.append(y16)
-        if split_ok:
-            # round 6, config.set_split_sites(3): BOTH contractions of the forward in split precision -- the hidden layer stays fp32 between them
-            # (what the bf16 mode's remaining gap at n_iter 8 sat in: profiles/r05_precision_sites.txt).  Saved for the backward, which is
-            # unchanged: the bf16 roundings of x, of the hidden activation and of its stored derivative.
-            # (the first launch's epilogue writes the fp32 hidden tile, its bf16 copy and the bf16 derivative: FabindGemmArgs.c2_bf16)
-            t32 = torch.empty((M, N1), dtype=torch.float32, device=x.device)
-            t = torch.empty((M, N1), dtype=ad, device=x.device)
-            D = torch.empty((M, N1), dtype=ad, device=x.device) if act == K.ACT_SILU else None
-            K.gemm(x, W32[0], bias=b1, A2=x2, act_epi=act, out=t32, out2=D, out16=t, force_x3=True)
-            y, _ = K.gemm(t32, W32[1], bias=b2, residual=residual, out_dtype=torch.float32, out16=y16, force_x3=True)
-            del t32
         else:
+            y16 = torch.empty((M, W2.shape[0]), dtype=torch.bfloat16, device=x.device) if holder is not None else None
             t = torch.empty((M, N1), dtype=ad, device=x.device)
             D = torch.empty((M, N1), dtype=ad, device=x.device) if act == K.ACT_SILU else None
-            K.gemm(xin, W1, bias=b1, A2=x2in, act_epi=act, out=t, out2=D)
-            y, _ = K.gemm(t, W2, bias=b2, residual=residual, out_dtype=torch.float32, out16=y16, p_drop=p_drop, seed=seed)
+            if split_ok:
+                # round 6, config.set_split_sites(3): BOTH contractions of the forward in split precision -- the hidden layer stays fp32 between
+                # them (what the bf16 mode's remaining gap at n_iter 8 sat in: profiles/r05_precision_sites.txt).  Saved for the backward, which
+                # is unchanged: the bf16 roundings of x, of the hidden activation and of its stored derivative.
+                # (the first launch's epilogue writes the fp32 hidden tile, its bf16 copy and the bf16 derivative: FabindGemmArgs.c2_bf16)
+                t32 = torch.empty((M, N1), dtype=torch.float32, device=x.device)
+                K.gemm(x, W32[0], bias=b1, A2=x2, act_epi=act, out=t32, out2=D, out16=t, force_x3=True)
+                y, _ = K.gemm(t32, W32[1], bias=b2, residual=residual, out_dtype=torch.float32, out16=y16, force_x3=True)
+                del t32
+            else:
+                K.gemm(xin, W1, bias=b1, A2=x2in, act_epi=act, out=t, out2=D)
+                y, _ = K.gemm(t, W2, bias=b2, residual=residual, out_dtype=torch.float32, out16=y16, p_drop=p_drop, seed=seed)
+        if holder is not None:
+            holder.append(y16)
         ctx.act, ctx.has_x2, ctx.has_res = act, x2 is not None, residual is not None
         ctx.res_is_x = residual is x
         ctx.sink_x, ctx.sink_res = _sink_of(x), _sink_of(residual)
         ctx.x2_dtype = x2.dtype if x2 is not None else None
         ctx.save_for_backward(xin, x2in, W1, W2, t, D)
-        ctx.W1t, ctx.W2t = getattr(W1, "_fab_T", None), getattr(W2, "_fab_T", None)
+        ctx.W1t, ctx.W2t = _stored_wt(W1), _stored_wt(W2)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         xin, x2in, W1, W2, t, D = ctx.saved_tensors
         dy = dy.contiguous()
-        md = mm_dtype()
         ni = ctx.needs_input_grad
-        if ctx.drop is not None:
-            dy16, db2 = _mul_dropmask_colsum(dy, ctx.drop[0], ctx.drop[1], md)   # d (W2 t + b2) = dy * keep / (1 - p): mask regenerated
-        elif dy.dtype != md and ni[4] and _db_in_tn(dy):
-            dy16, db2 = _mul_dact(dy, None, K.ACT_NONE, md), None           # cast only: the bias gradient rides with dW2's contraction
-        elif dy.dtype != md:
-            dy16, db2 = _mul_dact_colsum(dy, None, K.ACT_NONE, md)          # one pass: cast + bias gradient
-        else:
-            dy16, db2 = dy, None
-        if ni[4] and db2 is None:
-            dW2, db2 = _weight_grad(dy16, t, K.ACT_NONE, None, W2.dtype, want_db=True, W=W2)
-        else:
-            dW2 = _weight_grad(dy16, t, K.ACT_NONE, None, W2.dtype, W=W2) if ni[4] else None
-            db2 = db2 if db2 is not None else K.colsum(dy16)
+        # d (W2 t + b2) = dy (* keep / (1 - p), the mask regenerated) in the contractions' dtype
+        dy16, db2 = _dpre(dy, K.ACT_NONE, None, 1.0, ctx.drop, ni[5], ni[4])
+        dW2, db2 = _param_grads(dy16, t, None, W2, ni[4], ni[5], db2)
         aux, dact = (t, K.ACT_RELU) if ctx.act == K.ACT_RELU else (D, K.ACT_STORED_DERIV)
-        dpre, _ = K.gemm(dy16, ctx.W2t if ctx.W2t is not None else W2.t().contiguous(), aux=aux, dact=dact, out_dtype=md)      # (dy W2) * act'(pre)
-        if ni[2] and ni[3]:
-            dW1, db1 = _weight_grad(dpre, xin, K.ACT_NONE, x2in, W1.dtype, want_db=True, W=W1)
-        else:
-            db1 = K.colsum(dpre) if ni[3] else None
-            dW1 = _weight_grad(dpre, xin, K.ACT_NONE, x2in, W1.dtype, W=W1) if ni[2] else None
-        W1t = ctx.W1t if ctx.W1t is not None else W1.t().contiguous()
+        dmm, W2t = _padded_k(dy16, W2, ctx.W2t, (W2.shape[0] + 7) // 8 * 8)
+        dpre, _ = K.gemm(dmm, W2t, aux=aux, dact=dact, out_dtype=mm_dtype())                  # (dy W2) * act'(pre)
+        dW1, db1 = _param_grads(dpre, xin, x2in, W1, ni[2], ni[3])
+        W1t = _wt(ctx.W1t, W1)
         K1 = xin.shape[1]
         dres = dy if (ctx.has_res and ni[6]) else None
         dx = dx2 = None
@@ -529,7 +508,7 @@ class _MLP2(torch.autograd.Function):
             dres = ctx.sink_res.deposit(dres)
         if ctx.has_x2 and ni[1]:
             dx2, _ = K.gemm(dpre, W1t[K1:], out_dtype=torch.float32 if ctx.x2_dtype == torch.float32 else ctx.x2_dtype)
-        return dx, dx2, dW1, db1, dW2, (db2 if ni[5] else None), dres, None, None, None, None, None, None
+        return dx, dx2, dW1, db1, dW2, db2, dres, None, None, None, None, None, None
 
 
 def _chain_ok(x, x2, residual, W1, W2):
@@ -550,8 +529,7 @@ def mlp2(x, W1, b1, act, W2, b2, residual=None, x2=None, want16=False, p_drop=0.
     if _needs_grad(x, x2, W1, b1, W2, b2, residual):
         K.tn_hook(W1, b1, W2, b2)
         holder = [] if _want16(torch.float32, K.ACT_NONE, want16) else None
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0.0 else 0
-        y = _MLP2.apply(x, x2, W1, b1, W2, b2, residual, act, holder, p_drop, seed, W32, chain if W32 is not None else None)
+        y = _MLP2.apply(x, x2, W1, b1, W2, b2, residual, act, holder, p_drop, _drop_seed(p_drop), W32, chain if W32 is not None else None)
         return _attach_b16(y, holder[0] if holder else None)
     if W32 is not None:
         t = linear(x, W1, b1, act_epi=act, x2=x2, out_dtype=torch.float32, W32=W32[0])
@@ -571,8 +549,7 @@ class _MLP2Relu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W1, b1, W2, b2, residual, last_act, out_dtype, p_drop, seed1, seed2):
         assert not (last_act and residual is not None), "relu + dropout on the output: the residual is added by the caller"
-        thr = int(p_drop * 65536.0 + 0.5)
-        ctx.drop_scale = 1.0 / (1.0 - thr / 65536.0)
+        ctx.drop_scale = _drop_scale(p_drop)
         ad = act_dtype()
         M = x.shape[0]
         t = torch.empty((M, W1.shape[0]), dtype=ad, device=x.device)
@@ -586,44 +563,26 @@ class _MLP2Relu(torch.autograd.Function):
         ctx.res_dtype = residual.dtype if residual is not None else None
         ctx.sink_res = _sink_of(residual)
         ctx.save_for_backward(x, W1, W2, t, y if last_act else None)
+        ctx.W1t, ctx.W2t = _stored_wt(W1), _stored_wt(W2)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, W1, W2, t, y = ctx.saved_tensors
         dy = dy.contiguous()
-        md = mm_dtype()
         ni = ctx.needs_input_grad
         s = ctx.drop_scale
-        db2 = None
-        in_tn = ni[3] and ni[4] and _db_in_tn(dy)
-        if ctx.last_act:
-            dpre2, db2 = (_mul_dact(dy, y, K.ACT_RELU, md, s), None) if in_tn else _mul_dact_colsum(dy, y, K.ACT_RELU, md, s)
-        elif dy.dtype != md:
-            dpre2, db2 = (_mul_dact(dy, None, K.ACT_NONE, md), None) if in_tn else _mul_dact_colsum(dy, None, K.ACT_NONE, md)
-        else:
-            dpre2 = dy
-        dW2 = None
-        if ni[3] and db2 is None and ni[4]:
-            dW2, db2 = _weight_grad(dpre2, t, K.ACT_NONE, None, W2.dtype, want_db=True, W=W2)
-        elif ni[3]:
-            dW2 = _weight_grad(dpre2, t, K.ACT_NONE, None, W2.dtype, W=W2)
-        if ni[4] and db2 is None:
-            db2 = K.colsum(dpre2)
-        dpre1, _ = K.gemm(dpre2, _wt(W2), aux=t, dact=K.ACT_RELU, alpha=s, out_dtype=md)          # (dpre2 W2) * [t > 0] / (1 - p)
-        dW1 = db1 = None
-        if ni[1] and ni[2]:
-            dW1, db1 = _weight_grad(dpre1, x, K.ACT_NONE, None, W1.dtype, want_db=True, W=W1)
-        else:
-            dW1 = _weight_grad(dpre1, x, K.ACT_NONE, None, W1.dtype, W=W1) if ni[1] else None
-            db1 = K.colsum(dpre1) if ni[2] else None
-        dx = K.gemm(dpre1, _wt(W1), out_dtype=x.dtype)[0] if ni[0] else None
+        dpre2, db2 = _dpre(dy, K.ACT_RELU if ctx.last_act else K.ACT_NONE, y, s, None, ni[4], ni[3])
+        dW2, db2 = _param_grads(dpre2, t, None, W2, ni[3], ni[4], db2)
+        dpre1, _ = K.gemm(dpre2, _wt(ctx.W2t, W2), aux=t, dact=K.ACT_RELU, alpha=s, out_dtype=mm_dtype())   # (dpre2 W2) * [t > 0] / (1 - p)
+        dW1, db1 = _param_grads(dpre1, x, None, W1, ni[1], ni[2])
+        dx = K.gemm(dpre1, _wt(ctx.W1t, W1), out_dtype=x.dtype)[0] if ni[0] else None
         dres = None
         if ctx.has_res and ni[5]:
             dres = dy if dy.dtype == ctx.res_dtype else dy.to(ctx.res_dtype)
             if ctx.sink_res is not None:
                 dres = ctx.sink_res.deposit(dres)
-        return dx, dW1, db1, dW2, (db2 if ni[4] else None), dres, None, None, None, None, None
+        return dx, dW1, db1, dW2, db2, dres, None, None, None, None, None
 
 
 def mlp2_relu(x, W1, b1, W2, b2, last_act, residual=None, out_dtype=torch.float32, p_drop=0.0):
@@ -663,29 +622,33 @@ def _gemm_rowdot(x, W, b, u, act_pro, act_epi, store, p_drop=0.0, seed=0, fold=N
     return z, part
 
 
+def _rowdot_bwd(z, dpart, u, act_epi):
+    """Adjoint of part = row-dot(act_epi(z), u) over the stored z -> (dz = dpart u act_epi'(z) as z.dtype, du fp32); dpart [M, tiles] contiguous."""
+    M, N = z.shape
+    dz = torch.empty_like(z)
+    nchunk = _nchunk(M)
+    scratch = torch.empty((nchunk, N), dtype=torch.float32, device=z.device)
+    du = torch.empty(N, dtype=torch.float32, device=z.device)
+    check(load().fabind_rowdot_bwd(ptr(z), dt_code(z.dtype), ptr(dpart), dpart.shape[1], ptr(u), act_epi, M, N,
+                                   ptr(dz), ptr(du), ptr(scratch), nchunk, stream()), "fabind_rowdot_bwd")
+    return dz, du
+
+
 class _LinearRowdot(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, b, u, act_pro, act_epi):
         z, part = _gemm_rowdot(x, W, b, u, act_pro, act_epi, store=True)
-        ctx.act_pro, ctx.act_epi = act_pro, act_epi
+        ctx.act_pro, ctx.act_epi, ctx.Wt = act_pro, act_epi, _stored_wt(W)
         ctx.save_for_backward(x, W, u, z)
         return part
 
     @staticmethod
     def backward(ctx, dpart):
         x, W, u, z = ctx.saved_tensors
-        dpart = dpart.contiguous()
-        M, N = z.shape
-        dz = torch.empty_like(z)
-        nchunk = _nchunk(M)
-        scratch = torch.empty((nchunk, N), dtype=torch.float32, device=z.device)
-        du = torch.empty(N, dtype=torch.float32, device=z.device)
-        check(load().fabind_rowdot_bwd(ptr(z), dt_code(z.dtype), ptr(dpart), dpart.shape[1], ptr(u), ctx.act_epi, M, N,
-                                       ptr(dz), ptr(du), ptr(scratch), nchunk, stream()), "fabind_rowdot_bwd")
         assert ctx.act_pro == K.ACT_NONE
-        Wt = W.t().contiguous()
-        dx, _ = K.gemm(dz, Wt, out_dtype=x.dtype)
-        dW, db = _weight_grad(dz, x, K.ACT_NONE, None, W.dtype, want_db=True, W=W)
+        dz, du = _rowdot_bwd(z, dpart.contiguous(), u, ctx.act_epi)
+        dx, _ = K.gemm(dz, _wt(ctx.Wt, W), out_dtype=x.dtype)
+        dW, db = _param_grads(dz, x, None, W, True, True)
         return dx, dW, db, du, None, None
 
 
@@ -696,31 +659,17 @@ class _LinearRowdotDrop(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, b, u, p_drop, seed):
         z, part = _gemm_rowdot(x, W, b, u, K.ACT_NONE, K.ACT_RELU, store=True, p_drop=p_drop, seed=seed, post=True)
-        thr = int(p_drop * 65536.0 + 0.5)
-        ctx.scale = 1.0 / (1.0 - thr / 65536.0)
+        ctx.scale, ctx.Wt = _drop_scale(p_drop), _stored_wt(W)
         ctx.save_for_backward(x, W, u, z)
         return part
 
     @staticmethod
     def backward(ctx, dpart):
         x, W, u, z = ctx.saved_tensors
-        M, N = z.shape
-        dps = (dpart * ctx.scale).contiguous()                 # [M, tiles]: the 1 / (1 - p) of the kept positions
-        dz = torch.empty_like(z)
-        nchunk = _nchunk(M)
-        scratch = torch.empty((nchunk, N), dtype=torch.float32, device=z.device)
-        du = torch.empty(N, dtype=torch.float32, device=z.device)
-        check(load().fabind_rowdot_bwd(ptr(z), dt_code(z.dtype), ptr(dps), dps.shape[1], ptr(u), K.ACT_RELU, M, N,
-                                       ptr(dz), ptr(du), ptr(scratch), nchunk, stream()), "fabind_rowdot_bwd")
+        dz, du = _rowdot_bwd(z, (dpart * ctx.scale).contiguous(), u, K.ACT_RELU)       # [M, tiles]: the 1 / (1 - p) of the kept positions
         ni = ctx.needs_input_grad
-        dx = K.gemm(dz, _wt(W), out_dtype=x.dtype)[0] if ni[0] else None
-        dW = db = None
-        if ni[1] and ni[2]:
-            dW, db = _weight_grad(dz, x, K.ACT_NONE, None, W.dtype, want_db=True, W=W)
-        elif ni[1]:
-            dW = _weight_grad(dz, x, K.ACT_NONE, None, W.dtype, W=W)
-        elif ni[2]:
-            db = K.colsum(dz)
+        dx = K.gemm(dz, _wt(ctx.Wt, W), out_dtype=x.dtype)[0] if ni[0] else None
+        dW, db = _param_grads(dz, x, None, W, ni[1], ni[2])
         # (dz was formed from the PRE-scaled dpart, so it carries 1 / (1 - p) once, as it must; du = sum_r dpart z wants the
         #  unscaled dpart: the kernel's du is divided by the same factor)
         return dx, dW, db, (du / ctx.scale if ni[3] else None), None, None
@@ -735,11 +684,9 @@ def linear_rowdot(x, W, b, u, act_pro=K.ACT_NONE, act_epi=K.ACT_NONE, p_drop=0.0
         if p_drop > 0.0:
             assert act_pro == K.ACT_NONE and act_epi == K.ACT_RELU, "epilogue dropout under autograd: ReLU outputs only"
             assert b is not None, "linear_rowdot with epilogue dropout under autograd needs a bias"
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-            return _LinearRowdotDrop.apply(x, W, b, u, p_drop, seed)
+            return _LinearRowdotDrop.apply(x, W, b, u, p_drop, _drop_seed(p_drop))
         return _LinearRowdot.apply(x, W, b, u, act_pro, act_epi)
-    seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0.0 else 0
-    return _gemm_rowdot(x, W, b, u, act_pro, act_epi, store=False, p_drop=p_drop, seed=seed, fold=fold)[1]
+    return _gemm_rowdot(x, W, b, u, act_pro, act_epi, store=False, p_drop=p_drop, seed=_drop_seed(p_drop), fold=fold)[1]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -752,7 +699,7 @@ class _EdgeTail(torch.autograd.Function):
     def forward(ctx, Mm, Wc, bc, w3, rowptr, row, n_rows, act_epi):
         z, part = _gemm_rowdot(Mm, Wc, bc, w3, K.ACT_NONE, act_epi, store=True)
         agg = K.segment_sum(Mm, rowptr, n_rows)
-        ctx.act_epi = act_epi
+        ctx.act_epi, ctx.Wt = act_epi, _stored_wt(Wc)
         ctx.save_for_backward(Mm, Wc, w3, z, row)
         return part, agg
 
@@ -760,21 +707,15 @@ class _EdgeTail(torch.autograd.Function):
     def backward(ctx, dpart, dagg):
         Mm, Wc, w3, z, row = ctx.saved_tensors
         M, N = z.shape
-        dz = torch.empty_like(z)
-        nchunk = _nchunk(M)
-        scratch = torch.empty((nchunk, N), dtype=torch.float32, device=z.device)
-        du = torch.empty(N, dtype=torch.float32, device=z.device)
         if dpart is None:
             dpart = torch.zeros((M, (N + K.GEMM_BN - 1) // K.GEMM_BN), dtype=torch.float32, device=z.device)
-        dpart = dpart.contiguous()
-        check(load().fabind_rowdot_bwd(ptr(z), dt_code(z.dtype), ptr(dpart), dpart.shape[1], ptr(w3), ctx.act_epi, M, N,
-                                       ptr(dz), ptr(du), ptr(scratch), nchunk, stream()), "fabind_rowdot_bwd")
-        Wt = Wc.t().contiguous()
+        dz, du = _rowdot_bwd(z, dpart.contiguous(), w3, ctx.act_epi)
+        Wt = _wt(ctx.Wt, Wc)
         if dagg is not None:
             dM, _ = K.gemm(dz, Wt, residual=dagg.contiguous(), r_index=row, out_dtype=Mm.dtype)
         else:
             dM, _ = K.gemm(dz, Wt, out_dtype=Mm.dtype)
-        dW, dbc = _weight_grad(dz, Mm, K.ACT_NONE, None, Wc.dtype, want_db=True, W=Wc)
+        dW, dbc = _param_grads(dz, Mm, None, Wc, True, True)
         return dM, dW, dbc, du, None, None, None, None
 
 
@@ -871,7 +812,7 @@ def fused_edge(AB16, rhohat, w_r, W2, b2, Wc, bc, w3, H, g, p_drop=0.0, frags=No
     """(agg [N,H], s [E,1]) of the fused edge pipeline (bf16, or split bf16 on fp32 AB in 'bf16x3' mode); differentiable.  frags
     (bf16 mode): (W2p, Wcp[, W2Tp, WcTp]) fragment packs made ahead by kernels.pack_frag_multi (all four when a backward will come).  p_drop > 0:
     dropout on the messages (egnn.py:82) from a counter-based mask keyed by a seed drawn from torch's CPU generator (no device sync)."""
-    seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if p_drop > 0.0 else 0
+    seed = _drop_seed(p_drop)
     if _needs_grad(AB16, rhohat, w_r, W2, b2, Wc, bc, w3):
         K.tn_hook(W2, Wc)                    # (their gradients may be queued: kernels.gcl_edge_fused_bwd)
     if _cfg.get_precision() == "bf16x3" and _cfg.x3_edge_bf16() and AB16.dtype == torch.float32:
@@ -1117,7 +1058,7 @@ def drop_mix(h, hn, p_drop):
         return hn
     if (h.dtype == torch.float32 and hn.dtype == torch.float32 and h.is_contiguous() and hn.is_contiguous() and h.shape == hn.shape
             and h.numel() % 4 == 0 and h.is_cuda):
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        seed = _drop_seed(p_drop)
         if _needs_grad(h, hn):
             return _DropMix.apply(h, hn, p_drop, seed)
         out = torch.empty_like(h)
@@ -1603,7 +1544,7 @@ class _InterAttn(torch.autograd.Function):
                                                     bias_part, w_rk, w_rv, wcr, w3, clampv, s_ext, h16, deal=getattr(g, "int_deal", None))
         ctx.g, ctx.H, ctx.clampv, ctx.np = g, H, clampv, bias_part.shape[1]
         ctx.has_ext, ctx.has_cv = s_ext is not None, Wc is not None
-        ctx.sink_h = _sink_of(h)
+        ctx.sink_h, ctx.Wct = _sink_of(h), (_stored_wt(Wc) if Wc is not None else None)
         ctx.save_for_backward(qkv, cv, d, rhohat, w_rk, w_rv, wcr, w3, alpha, cvs, v_in, Wc)
         ctx.mark_non_differentiable(alpha)
         return h_out, x_out, alpha
@@ -1648,20 +1589,10 @@ class _InterAttn(torch.autograd.Function):
         dw = [dw_all[i * H:(i + 1) * H] for i in range(4)]
         dWc = dbc = None
         if ctx.has_cv:                                               # adjoint of cv = V Wc^T + bc, dV added to dqkv[:, 2H:]
-            md = mm_dtype()
-            dpre, dbc = dcv, None
-            if dcv.dtype != md:
-                in_tn = ctx.needs_input_grad[15] and ctx.needs_input_grad[16] and _db_in_tn(dcv)
-                dpre, dbc = _mul_dact_colsum(dcv, None, K.ACT_NONE, md) if not in_tn else (_mul_dact(dcv, None, K.ACT_NONE, md), None)
-            K.gemm(dpre, Wc.t().contiguous(), out=dqkv[:, 2 * H:], accumulate=True)
-            if ctx.needs_input_grad[15] and ctx.needs_input_grad[16] and dbc is None:
-                dWc, dbc = _weight_grad(dpre, v_in, K.ACT_NONE, None, Wc.dtype, want_db=True, W=Wc)
-            elif ctx.needs_input_grad[15]:
-                dWc = _weight_grad(dpre, v_in, K.ACT_NONE, None, Wc.dtype, W=Wc)
-            if ctx.needs_input_grad[16]:
-                dbc = dbc if dbc is not None else K.colsum(dpre)
-            else:
-                dbc = None
+            ni = ctx.needs_input_grad
+            dpre, dbc = _dpre(dcv, K.ACT_NONE, None, 1.0, None, ni[16], ni[15])
+            K.gemm(dpre, _wt(ctx.Wct, Wc), out=dqkv[:, 2 * H:], accumulate=True)
+            dWc, dbc = _param_grads(dpre, v_in, None, Wc, ni[15], ni[16], dbc)
             dcv = None
         if ctx.sink_h is not None and ctx.needs_input_grad[2]:
             dh_out = ctx.sink_h.deposit(dh_out)           # h_out = h + ...: the residual gradient joins h's shared buffer

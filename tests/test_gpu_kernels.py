@@ -741,25 +741,51 @@ def test_shared_gradient_buffer_matches_plain_autograd(case):
     assert float((g1 - r1).abs().max()) <= 1e-5 * float(r1.abs().max())
 
 
-@pytest.mark.parametrize("prec,tol", [("fp32", 2e-4), ("bf16", 3e-2)])
-@pytest.mark.parametrize("act", ["relu", "silu"])
-@pytest.mark.parametrize("with_x2,with_sink", [(False, False), (True, False), (False, True), (True, True)])
-def test_mlp2_node_matches_autograd(prec, tol, act, with_x2, with_sink):
+def _with_db_from(names, cases, extra=(), id_fields=None):
+    """parametrize(names + ",db_from") over cases x ("tn", "pass"): a "tn" case keeps the id it had before db_from existed (its first
+    id_fields parameter values joined by "-", a tuple as <name><index>), its "pass" twin appends "-pass"; extra: further
+    (values..., db_from, id) cases."""
+    def one(name, i, v):
+        return "%s%d" % (name, i) if isinstance(v, tuple) else str(v)
+    first = names.split(",")[0]
+    ps = [pytest.param(*c, db, id="-".join(one(first, i, v) for v in c[:id_fields]) + ("" if db == "tn" else "-pass")) for db in ("tn", "pass") for i, c in enumerate(cases)]
+    return pytest.mark.parametrize(names + ",db_from", ps + [pytest.param(*e[:-1], id=e[-1]) for e in extra])
+
+
+def _db_from(monkeypatch, db_from):
+    """Which side of ops.DB_IN_TN_ROWS a unit-sized Linear adjoint sees in bf16: 'tn' (as shipped: every shape here is below it, the bias
+    gradient rides with the queued TN contraction) or 'pass' (threshold 0: the bias gradient comes from the fused pass over dy)."""
+    from fabind_amd import ops
+    assert db_from in ("tn", "pass")
+    if db_from == "pass":
+        monkeypatch.setattr(ops, "DB_IN_TN_ROWS", 0)
+
+
+@_with_db_from("with_x2,with_sink,act,prec,tol,No",
+               [(x2, sink, act, prec, tol, 128) for prec, tol in (("fp32", 2e-4), ("bf16", 3e-2)) for act in ("relu", "silu")
+                for x2, sink in ((False, False), (True, False), (False, True), (True, True))],
+               # an output width that is a multiple of 2, not of 4 (nor of the GEMM's 8)
+               extra=[(False, False, "relu", "fp32", 2e-4, 126, "tn", "False-False-relu-fp32-0.0002-width126")], id_fields=5)
+def test_mlp2_node_matches_autograd(prec, tol, act, with_x2, with_sink, db_from, No, monkeypatch):
     """ops.mlp2 (Linear -> act -> Linear (+ residual) as one autograd node: activation adjoint inside the GEMM epilogue,
     residual gradient folded into the input-gradient GEMM or x's shared buffer) against plain torch autograd -- forward,
-    d x, d x2, all four parameter gradients; with and without a second consumer of x sharing the gradient buffer."""
+    d x, d x2, all four parameter gradients; with and without a second consumer of x sharing the gradient buffer; the bias
+    gradients from either side of ops.DB_IN_TN_ROWS (_db_from); an output width No below x's (the residual is then x's first No
+    columns) that neither the column-sum pass nor the TN kernel nor an input-gradient GEMM's contraction takes as it is."""
     from fabind_amd import engine, kernels as K, ops
     dev = _dev()
+    _db_from(monkeypatch, db_from)
     engine.set_precision(prec)
     try:
         g = torch.Generator().manual_seed(7)
         M, Hh, K2, N1 = 1000, 128, 64, 256
+        cut = (lambda t_: t_) if No == Hh else (lambda t_: t_[:, :No])
         x = torch.randn(M, Hh, generator=g)
         x2 = torch.randn(M, K2, generator=g) if with_x2 else None
         W1 = torch.randn(N1, Hh + (K2 if with_x2 else 0), generator=g) / 12
-        b1, W2, b2 = torch.randn(N1, generator=g) * 0.1, torch.randn(Hh, N1, generator=g) / 16, torch.randn(Hh, generator=g) * 0.1
+        b1, W2, b2 = torch.randn(N1, generator=g) * 0.1, torch.randn(No, N1, generator=g) / 16, torch.randn(No, generator=g) * 0.1
         W3 = torch.randn(64, Hh, generator=g) / 12                       # the second consumer of x
-        cot = torch.randn(M, Hh, generator=g)
+        cot = torch.randn(M, No, generator=g)
         fa = torch.relu if act == "relu" else torch.nn.functional.silu
         leaves = [t.clone().requires_grad_(True) for t in (x, W1, b1, W2, b2, W3)] + ([x2.clone().requires_grad_(True)] if with_x2 else [])
         xr, W1r, b1r, W2r, b2r, W3r = leaves[:6]
@@ -767,7 +793,7 @@ def test_mlp2_node_matches_autograd(prec, tol, act, with_x2, with_sink):
         # 2^-9 of zero differ and single gradient entries move by O(1) of a term
         rb = (lambda t_: t_ + (t_.bfloat16().float() - t_).detach()) if prec == "bf16" else (lambda t_: t_)
         xin = torch.cat([rb(xr), rb(leaves[6])], 1) if with_x2 else rb(xr)
-        yr = rb(fa(xin @ rb(W1r).T + b1r)) @ rb(W2r).T + b2r + xr
+        yr = rb(fa(xin @ rb(W1r).T + b1r)) @ rb(W2r).T + b2r + cut(xr)
         extra = (xr @ W3r.T).pow(2).sum() if with_sink else 0.0
         ((yr * cot).sum() + extra).backward()
         wd = ops.mm_dtype()
@@ -775,7 +801,7 @@ def test_mlp2_node_matches_autograd(prec, tol, act, with_x2, with_sink):
         xd, W1d, b1d, W2d, b2d, W3d = dl[:6]
         xs = ops.shared_grad(xd) if with_sink else xd
         code = K.ACT_RELU if act == "relu" else K.ACT_SILU
-        y = ops.mlp2(xs, W1d.to(wd), b1d, code, W2d.to(wd), b2d, residual=xs, x2=dl[6] if with_x2 else None)
+        y = ops.mlp2(xs, W1d.to(wd), b1d, code, W2d.to(wd), b2d, residual=cut(xs), x2=dl[6] if with_x2 else None)
         extra = ops.linear(xs, W3d.to(wd)).pow(2).sum() if with_sink else 0.0
         ((y * cot.to(dev)).sum() + extra).backward()
         assert float((y.detach().cpu() - yr.detach()).abs().max()) <= tol * float(yr.abs().max())
@@ -924,14 +950,15 @@ def test_layernorm_rows_and_adjoint(R, C, ld, dt):
     assert (bd.grad.cpu() - br.grad).abs().max() <= 1e-3 * max(1.0, float(br.grad.abs().max()))
 
 
-@pytest.mark.parametrize("mode", ["bf16", "fp32"])
-def test_linear_relu_with_epilogue_dropout_under_autograd(mode):
+@_with_db_from("mode", [("bf16",), ("fp32",)])
+def test_linear_relu_with_epilogue_dropout_under_autograd(mode, db_from, monkeypatch):
     """ops.linear(act_epi=RELU, p_drop > 0) under autograd (FABind+ training: every LN-MLP is Linear -> ReLU -> Dropout,
     model_utils.py:10-74): the mask is applied in the GEMM epilogue and never stored; the backward takes it from the zeros of the saved
     output.  Checked against torch autograd of relu(x W^T + b) * mask / (1 - p) with the epilogue's hash mask restated on the host."""
     from fabind_amd import config, ops
     from fabind_amd import kernels as K
     dev = _dev()
+    _db_from(monkeypatch, db_from)
     config.set_precision(mode)
     try:
         g = torch.Generator().manual_seed(5)
@@ -990,13 +1017,14 @@ def _hash_keep(seed, M, N, p):
 
 
 @pytest.mark.parametrize("dims", [(900, 136, 264, 128), (1100, 128, 256, 128)])      # register-staged fallback GEMM / LDS-DMA pipelined GEMM
-@pytest.mark.parametrize("last_act,with_res,p", [(True, False, 0.25), (False, True, 0.25), (False, False, 0.0), (True, False, 0.0)])
-def test_relu_mlp_as_one_autograd_node(last_act, with_res, p, dims):
+@_with_db_from("last_act,with_res,p", [(True, False, 0.25), (False, True, 0.25), (False, False, 0.0), (True, False, 0.0)])
+def test_relu_mlp_as_one_autograd_node(last_act, with_res, p, dims, db_from, monkeypatch):
     """ops.mlp2_relu (the two Linears of a FABind+ LN-MLP, model_utils.py:10-74, as one autograd node: ReLU + dropout in both GEMM
     epilogues, the hidden layer's adjoint inside the input-gradient GEMM of the second Linear) against torch autograd with the
     epilogue masks restated on the host."""
     from fabind_amd import config, ops
     dev = _dev()
+    _db_from(monkeypatch, db_from)
     config.set_precision("bf16")
     try:
         g = torch.Generator().manual_seed(17)
@@ -1374,7 +1402,7 @@ def test_gemm_tn_multi_matches_single_launches():
 
 @pytest.mark.parametrize("case", ["composed_weight", "weight_used_twice", "leaf_weight_accumulates", "x2_and_bias"])
 def test_queued_weight_gradients_are_flushed_before_anything_reads_them(case):
-    """The contract of the weight-gradient queue under autograd (ops._tn_queue): a queued gradient is written before its first reader --
+    """The contract of the weight-gradient queue under autograd (ops._tn): a queued gradient is written before its first reader --
     a torch op that composed the weight from parameters, autograd's own sum when one weight feeds two Linears, the accumulation into
     an existing .grad, the end of the backward pass.  Each case against the same graph with the queue switched off."""
     from fabind_amd import config, kernels as K, ops
@@ -1560,14 +1588,15 @@ def test_row_gathers_with_copy_and_segment_sum_adjoints_match_index_select():
 
 
 @pytest.mark.parametrize("prec", ["bf16", "bf16x3"])
-@pytest.mark.parametrize("with_res", [True, False])
-def test_linear_with_epilogue_dropout_ahead_of_the_residual_under_autograd(prec, with_res):
+@_with_db_from("with_res", [(True,), (False,)])
+def test_linear_with_epilogue_dropout_ahead_of_the_residual_under_autograd(prec, with_res, db_from, monkeypatch):
     """Round 5, train mode: y = r + drop(x W^T + b) (nn.Dropout ahead of `h + ...`: FABind/fabind/models/egnn.py:106, cross_att.py:128)
     as ONE GEMM with the counter-based mask in its fp32 epilogue; the adjoint regenerates the mask from (seed, row, col)
     (fabind_mul_dropmask_colsum).  Checked against the explicit formula with the mask read off the forward output: values, drop rate,
     and the gradients of x, W, b and the residual; the bf16 operand copy of y carries the same values."""
     from fabind_amd import config, ops
     dev = torch.device("cuda:0")
+    _db_from(monkeypatch, db_from)
     g = torch.Generator().manual_seed(7)
     M, Kd, N, pd = 3001, 256, 512, 0.1
     x0, W0 = torch.randn(M, Kd, generator=g).to(dev), (torch.randn(N, Kd, generator=g) / Kd ** 0.5).to(dev)

@@ -410,6 +410,91 @@ def test_rows_hadamard_csr_lists_every_pair_under_both_rows():
     assert int(rp[36]) == int(rp[37])                      # rows 35, 36 have no pair
 
 
+def test_linear_adjoint_decisions_are_one_table(monkeypatch):
+    """The two decisions every Linear's adjoint makes (ops._dpre_plan: which pass over dy, and does it carry the bias gradient;
+    ops._wgrad_plan: which contraction computes dW, and does the bias gradient ride with it) as pure functions of dtype, shape, strides,
+    alignment, the precision mode and the switches -- pinned on both sides of every condition against a restatement of the rules:
+    rows around DB_IN_TN_ROWS and around the split mode's 256-row floor, widths 8 and 6, dy fp32 / bf16 in all three modes, the four
+    (want_dW, want_db) combinations, drop mask, activation, FUSE_DB_TN, TN_DEFER, x3_backward.  The adjoint-side counterpart of the
+    fabind_gemm_plan assertions."""
+    import itertools
+    from fabind_amd import config, ops
+    from fabind_amd import kernels as K
+    f32, bf = torch.float32, torch.bfloat16
+    assert ops.DB_IN_TN_ROWS == 32768
+    ROWS, KX = (255, 256, 32768, 32769), 16
+    buf = {(R, C, dt): torch.empty((R, C), dtype=dt) for R in ROWS for C in (8, 6, KX) for dt in (f32, bf)}
+
+    def want(mode, x3b, fuse, defer, dy, act, drop, want_dW, want_db):
+        R, C = dy.shape
+        md = bf if mode == "bf16" else f32
+        kind = "dropmask" if drop else "act" if act else "cast" if dy.dtype != md else "none"
+        in_tn = defer and R <= 32768 and md == bf
+        in_pass = want_db and (kind == "dropmask" or (kind != "none" and C % 4 == 0 and not (want_dW and in_tn)))
+        if mode == "bf16x3" and x3b == "bf16" and C % 8 == 0 and R >= 256:
+            path, rides = "x3_tn", fuse and C % 4 == 0
+        elif md == bf and C % 8 == 0:
+            path, rides = "tn", fuse
+        else:
+            path, rides = "nt", False
+        db_from = None if not want_db else "pass" if in_pass else "tn" if (want_dW and rides) else "colsum"
+        return kind, db_from, (path if want_dW else None)
+
+    def got(dy, act, drop, want_dW, want_db):
+        kind, in_pass = ops._dpre_plan(dy, K.ACT_RELU if act else K.ACT_NONE, (0.1, 7) if drop else None, want_db, want_dW)
+        md = ops.mm_dtype()
+        dpre = dy if kind == "none" else buf[(dy.shape[0], dy.shape[1], md)]          # what the pass writes: mm dtype, contiguous
+        assert not (in_pass and not want_db) and dpre.dtype == md
+        path, rides = ops._wgrad_plan(dpre, buf[(dy.shape[0], KX, md)], None, want_db and not in_pass) if want_dW else (None, False)
+        return kind, (None if not want_db else "pass" if in_pass else "tn" if rides else "colsum"), path
+
+    mode0, x3b0 = config.get_precision(), ("bf16" if config.x3_backward_bf16() else "exact")
+    try:
+        n = 0
+        for mode, x3b, fuse, defer in itertools.product(config.MODES, ("bf16", "exact"), (True, False), (True, False)):
+            config.set_precision(mode)
+            config.set_x3_backward(x3b)
+            monkeypatch.setattr(ops, "FUSE_DB_TN", fuse)
+            monkeypatch.setattr(K, "TN_DEFER", defer)
+            for R, C, dt, act, drop, want_dW, want_db in itertools.product(ROWS, (8, 6), (f32, bf), (False, True), (False, True),
+                                                                           (False, True), (False, True)):
+                case = (mode, x3b, fuse, defer, R, C, dt, act, drop, want_dW, want_db)
+                assert got(buf[(R, C, dt)], act, drop, want_dW, want_db) == want(mode, x3b, fuse, defer, buf[(R, C, dt)], act, drop, want_dW, want_db), case
+                n += 1
+        assert n == 3 * 2 * 2 * 2 * 4 * 2 * 2 * 2 * 2 * 2 * 2
+        # a few rows of the table spelled out (bf16 mode, everything on): the cast of an fp32 dy
+        config.set_precision("bf16")
+        config.set_x3_backward("bf16")
+        monkeypatch.setattr(ops, "FUSE_DB_TN", True)
+        monkeypatch.setattr(K, "TN_DEFER", True)
+        assert got(buf[(32768, 8, f32)], False, False, True, True) == ("cast", "tn", "tn")          # small batch: db rides with the queued TN
+        assert got(buf[(32769, 8, f32)], False, False, True, True) == ("cast", "pass", "tn")        # large batch: db from the fused pass
+        assert got(buf[(32768, 8, f32)], False, False, False, True) == ("cast", "pass", None)       # no dW: nothing to ride with
+        assert got(buf[(32769, 6, f32)], False, False, True, True) == ("cast", "colsum", "nt")      # C % 4: the fused pass does not apply
+        assert got(buf[(32768, 8, bf)], False, False, True, True) == ("none", "tn", "tn")
+        assert got(buf[(32768, 8, bf)], False, False, False, True) == ("none", "colsum", None)
+        assert got(buf[(32768, 8, f32)], False, True, True, False) == ("dropmask", None, "tn")
+        monkeypatch.setattr(ops, "DB_IN_TN_ROWS", 0)                                                # (what the GPU tests' db_from="pass" sets)
+        assert got(buf[(255, 8, f32)], True, False, True, True) == ("act", "pass", "tn")
+        monkeypatch.setattr(ops, "DB_IN_TN_ROWS", 32768)
+        # strides and alignment: the TN kernel wants 16-byte aligned rows
+        d = buf[(256, 8, bf)]
+        wide = torch.empty((256, 24), dtype=bf)
+        assert ops._wgrad_plan(d, wide[:, :16], None, True) == ("tn", True)
+        assert ops._wgrad_plan(d, wide[:, 1:17], None, True) == ("nt", False)                       # data pointer 2 bytes off
+        assert ops._wgrad_plan(d, torch.empty((256, 20), dtype=bf)[:, :16], None, True) == ("nt", False)   # row stride 40 bytes
+        assert ops._wgrad_plan(d, buf[(256, KX, bf)], buf[(256, 6, bf)], True) == ("nt", False)     # second operand of odd width
+        assert ops._wgrad_plan(d, buf[(256, KX, bf)], buf[(256, 8, bf)], True) == ("tn", True)
+        config.set_precision("bf16x3")
+        assert ops._wgrad_plan(buf[(256, 8, f32)], buf[(256, KX, f32)], None, True) == ("x3_tn", True)
+        assert ops._wgrad_plan(buf[(255, 8, f32)], buf[(255, KX, f32)], None, True) == ("nt", False)
+        config.set_x3_backward("exact")
+        assert ops._wgrad_plan(buf[(256, 8, f32)], buf[(256, KX, f32)], None, True) == ("nt", False)
+    finally:
+        config.set_precision(mode0)
+        config.set_x3_backward(x3b0)
+
+
 def test_bench_reports_rooflines_by_the_survey_classification():
     """bench.py (round 6): WHICH roofline a kernel family is reported against follows SURVEY 8(d)'s classification of the
     operation (bound_of), not whichever fraction is larger; the fraction is reproducible from flops (or 8(d) compulsory bytes), launch

@@ -2158,3 +2158,96 @@ def pair_dist(xp, xc, blocks, scale=1.0, lo=0.0, hi=10.0):
     xp, xc = xp.float().contiguous(), xc.float().contiguous()
     assert xp.shape[0] == blocks.n_prows and xc.shape[0] == blocks.n_crows
     return _PairDist.apply(xp, xc, blocks, float(scale), float(lo), float(hi))
+
+
+# ------------------------------------------------------------------------------------------------
+# FABind+ confidence training (csrc/ranking.hip): per-sample pose statistics and the pairwise ranking loss over the copies of a complex
+# (reference utils/training_confidence.py:41-77 / :215-252 -- a python double loop of S(S-1)/2 scalar autograd steps)
+# ------------------------------------------------------------------------------------------------
+RANK_MODES = {"logsigmoid": 0, "dynamic_hinge": 1}
+RANK_MAX_GROUP = 1024
+COUNT_NAMES = ("ranked_right", "pairs", "hit", "confidence_correct")
+
+
+def atom_offsets(compound_batch, B):
+    """int32 [B + 1] atom offsets of a sorted per-atom sample id vector, on the device (a binary search per sample: no read-back)."""
+    cb = compound_batch.to(torch.int32).contiguous()
+    keys = torch.arange(B + 1, dtype=torch.int32, device=cb.device)
+    out = torch.empty(B + 1, dtype=torch.int32, device=cb.device)
+    check(load().fabind_lower_bound(ptr(cb), cb.numel(), ptr(keys), B + 1, ptr(out), stream()), "fabind_lower_bound")
+    return out
+
+
+def pose_stats(pred, truth, compound_batch, B):
+    """(rmsd [B], centroid distance [B]) of predicted against true ligand coordinates [N, 3]; compound_batch [N]: the sorted sample
+    id of every atom (training_confidence.py:41-46).  No gradient: the reference detaches the coordinates.  Two launches."""
+    if pred.dim() != 2 or pred.shape[1] != 3 or tuple(truth.shape) != tuple(pred.shape):
+        raise ValueError("pose_stats: pred and truth must both be [N, 3]; got %s and %s" % (tuple(pred.shape), tuple(truth.shape)))
+    if compound_batch.dim() != 1 or compound_batch.numel() != pred.shape[0]:
+        raise ValueError("pose_stats: compound_batch must be [N = %d]; got %s" % (pred.shape[0], tuple(compound_batch.shape)))
+    if B < 0 or pred.shape[0] >= 2 ** 31 // 3:
+        raise ValueError("pose_stats: B >= 0 and fewer than 2^31 / 3 atoms")
+    p, t = pred.detach().float().contiguous(), truth.detach().float().contiguous()
+    aoff = atom_offsets(compound_batch, B)
+    rmsd = torch.empty(B, dtype=torch.float32, device=p.device)
+    cdis = torch.empty_like(rmsd)
+    check(load().fabind_pose_stats(ptr(p), ptr(t), ptr(aoff), B, ptr(rmsd), ptr(cdis), stream()), "fabind_pose_stats")
+    return rmsd, cdis
+
+
+class _RankLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, rmsd, group_off, G, mode, with_ce):
+        dev = scores.device
+        terms = torch.empty((G, 3), dtype=torch.float32, device=dev)
+        counts = torch.empty((G, 4), dtype=torch.int32, device=dev)
+        d_scores = torch.empty_like(scores)
+        check(load().fabind_rank_loss_fwd(ptr(scores), ptr(rmsd), ptr(group_off), G, mode, int(with_ce), ptr(terms), ptr(d_scores),
+                                          ptr(counts), stream()), "fabind_rank_loss_fwd")
+        mean = terms.mean(0)                                       # (ranking, ce, ranking + ce), mean over the groups
+        ranking, ce, loss = mean.unbind(0)
+        ctx.save_for_backward(d_scores)
+        ctx.G = G
+        ctx.mark_non_differentiable(ranking, ce, terms, counts)
+        return loss, ranking, ce, terms, counts
+
+    @staticmethod
+    def backward(ctx, g_loss, *unused):
+        d_scores, = ctx.saved_tensors
+        return d_scores * (g_loss if ctx.G == 1 else g_loss / ctx.G), None, None, None, None, None
+
+
+def group_offsets(B, group_size, dev):
+    """int32 [G + 1] offsets of consecutive groups of `group_size` samples (None: one group of B), checked on the host: the ranking
+    kernel holds a group in LDS, 2 <= size <= 1024.  -> (offsets on the device, G).  Built by a launch, not by a copy."""
+    S = B if group_size is None else int(group_size)
+    if S < 2 or S > RANK_MAX_GROUP:
+        raise ValueError("ranking loss: a group holds 2 to %d samples; got %d" % (RANK_MAX_GROUP, S))
+    if B < S or B % S:
+        raise ValueError("ranking loss: %d samples do not split into groups of %d" % (B, S))
+    return torch.arange(0, B + 1, S, dtype=torch.int32, device=dev), B // S
+
+
+def rank_loss(scores, rmsd, group_size=None, mode="logsigmoid", with_ce=False, group_sizes=None):
+    """Pairwise ranking loss of FABind+'s confidence head (training_confidence.py:48-73): within every group the sample with the lower
+    rmsd should score higher; `mode` logsigmoid / dynamic_hinge, `with_ce` adds the BCE of the score against [rmsd < 2 A].
+    scores [B] (differentiable), rmsd [B] (data).  Groups: consecutive runs of `group_size` samples (None: the whole batch), or
+    `group_sizes`, a host list of ragged sizes.  Ties in rmsd resolve by index (the stable form of the reference's argsort).
+    -> (loss, ranking, ce: scalars, the mean over groups; terms [G, 3]; counts int32 [G, 4], see COUNT_NAMES).
+    ONE launch forward; the adjoint is a multiply of the derivative the forward kernel stored."""
+    if mode not in RANK_MODES:
+        raise ValueError("ranking loss mode must be one of %s; got %r" % (sorted(RANK_MODES), mode))
+    if scores.dim() != 1 or tuple(rmsd.shape) != tuple(scores.shape):
+        raise ValueError("rank_loss: scores and rmsd must both be [B]; got %s and %s" % (tuple(scores.shape), tuple(rmsd.shape)))
+    B = scores.shape[0]
+    if group_sizes is not None:
+        sizes = [int(v) for v in group_sizes]
+        if not sizes or min(sizes) < 2 or max(sizes) > RANK_MAX_GROUP:
+            raise ValueError("ranking loss: a group holds 2 to %d samples; got %s" % (RANK_MAX_GROUP, sizes))
+        if sum(sizes) != B:
+            raise ValueError("ranking loss: group sizes %s do not add up to %d samples" % (sizes, B))
+        from .param_pack import upload
+        goff, G = upload(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32), scores.device, torch.int32), len(sizes)
+    else:
+        goff, G = group_offsets(B, group_size, scores.device)
+    return _RankLoss.apply(scores.float().contiguous(), rmsd.detach().float().contiguous(), goff, G, RANK_MODES[mode], bool(with_ce))

@@ -364,9 +364,11 @@ def train_step(model, data, optimizer, compute_loss, world=1, clip=1.0, stage=1,
     reducer: a GradReducer over the model's parameters (overlaps the all-reduce with backward); without one the
     gradients are reduced after backward.
     optimizer: an `optim.FusedAdam` takes the clip into its own step (no `clip_grad_norm_` pass; .grad keeps the unclipped gradient);
-    every other optimizer is clipped and stepped as the reference does."""
+    every other optimizer is clipped and stepped as the reference does.
+    FABind+ confidence training: a model that returns the 7-tuple, with compute_loss = plus.models.compute_confidence_loss."""
     out = model(data, stage=stage, train=True)
-    bad = torch.stack([torch.isnan(t).any() for t in (out[0], out[2], out[3], out[4], out[8])]).any()
+    guard = (0, 2, 3, 4, 8) if len(out) > 7 else (0, 2, 5)       # (FABind+ confidence training's 7-tuple: coordinates, pocket logits, score)
+    bad = torch.stack([torch.isnan(out[i]).any() for i in guard]).any()
     if all_ranks_agree_to_skip(bad, world):
         return None
     loss, terms = compute_loss(out, data)

@@ -1,0 +1,97 @@
+"""FABind+ confidence metrics and top-N selection without per-pair host synchronisation.
+
+`ConfidenceEvaluator` accumulates what the reference's confidence loops accumulate (FABind_plus/fabind/utils/training_confidence.py
+:215-326 -- validation; :41-149 is the same bookkeeping around the training step) and returns the dictionary of :313-326.  The
+reference appends one python float per PAIR of copies (`ranking_accuracy_list`, a `.item()`-style read per pair) and reads three
+losses back per batch; here the ranking kernel (csrc/ranking.hip) returns the four counts of a group, the partial sums stay on the
+device, and `compute()` reads everything back in one transfer.
+
+`select_by_confidence` / `sampling_metrics` are the top-N evaluation of test_sampling_fabind.py:159-191 (FABind+'s sampling table)
+on [S, B] tensors instead of S text files; they run once per evaluation and are plain torch."""
+import torch
+
+from .models.model import confidence_terms
+
+
+def _summary(x, prefix):
+    q = [torch.quantile(x, p) for p in (0.25, 0.50, 0.75)]
+    return [prefix, prefix + " < 2A", prefix + " < 5A", prefix + " 25%", prefix + " 50%", prefix + " 75%"], \
+        [x.mean(), (x < 2).float().mean(), (x < 5).float().mean()] + q
+
+
+class ConfidenceEvaluator:
+    """`update` once per batch with the model's 7-tuple, `compute` once at the end.  `update` issues no host synchronisation,
+    `compute` exactly one.  args: `ranking_loss` (logsigmoid / dynamic_hinge) and `keep_cls_2A`, as compute_confidence_loss reads them.
+
+    The reference's conventions are kept as they are: the three losses are averaged with weight len(scores) per batch;
+    `confidence_accuracy` compares the FIRST score of a group with every copy's [rmsd < 2 A] (training_confidence.py:252);
+    `hit_rate` and `confidence_accuracy` divide by the number of samples, `ranking_accuracy` by the number of pairs."""
+
+    def __init__(self, args=None):
+        self.mode = getattr(args, "ranking_loss", "logsigmoid") if args is not None else "logsigmoid"
+        self.with_ce = bool(getattr(args, "keep_cls_2A", False)) if args is not None else False
+        self.reset()
+
+    def reset(self):
+        self._rmsd, self._cdis = [], []
+        self._loss = None            # float64 [3]: sum of len(scores) * (loss, ranking, ce)
+        self._count = None           # int64 [5]: ranked_right, pairs, hit, confidence_correct, skipped samples
+        self.samples = self.less5 = 0
+
+    @torch.no_grad()
+    def update(self, out, coords_true, group_size=None, rmsd=None):
+        loss, info = confidence_terms(out, coords_true, self.mode, self.with_ce, group_size, rmsd)
+        logits, mask = out[2], out[3]
+        B = info["rmsd"].shape[0]
+        # training_confidence.py:272-279: a sample whose pocket head predicts no residue at all
+        skipped = (((logits.sigmoid().round() == 1) & mask.bool()).sum(1) == 0).sum()
+        part = torch.stack([loss, info["ranking"], info["ce"]]).double() * B
+        cnt = torch.cat([info["counts"].sum(0, dtype=torch.int64), skipped.reshape(1)])
+        self._loss = part if self._loss is None else self._loss + part
+        self._count = cnt if self._count is None else self._count + cnt
+        self._rmsd.append(info["rmsd"])
+        self._cdis.append(info["centroid_dis"])
+        self.samples += int(mask.shape[0])
+        self.less5 += int(out[4])
+        return loss
+
+    def compute(self):
+        if not self._rmsd:
+            raise RuntimeError("ConfidenceEvaluator.compute: no batch has been added")
+        rmsd, cdis = torch.cat(self._rmsd), torch.cat(self._cdis)
+        names_r, vals_r = _summary(rmsd, "rmsd")
+        names_c, vals_c = _summary(cdis, "centroid_dis")
+        flat = torch.cat([torch.stack(vals_r + vals_c).double(), self._loss, self._count.double()]).tolist()   # the one read-back
+        n = rmsd.shape[0]
+        metrics = {"samples": self.samples, "skip_samples": int(flat[-1]), "keepNode < 5": self.less5}
+        metrics.update(zip(names_r + names_c, flat[:12]))
+        tot, ranking, ce = flat[12:15]
+        right, pairs, hit, conf = flat[15:19]
+        metrics.update({"confidence_loss": tot / n, "ranking_loss": ranking / n, "confidence_ce_loss": ce / n,
+                        "confidence_accuracy": conf / n, "ranking_accuracy": right / pairs if pairs > 0 else 0.,
+                        "hit_rate": hit / n})
+        return metrics
+
+
+def select_by_confidence(rmsd, cdis, conf, top_n=1):
+    """test_sampling_fabind.py:163-175: per complex, among its `top_n` most confident samples, the minimum RMSD and the minimum
+    centroid distance (each minimum on its own, as the reference takes them).  rmsd, cdis, conf: [S, B] (S samples of B complexes).
+    -> (rmsd [B], centroid distance [B]).  Equal confidences keep their sample order."""
+    if rmsd.dim() != 2 or tuple(cdis.shape) != tuple(rmsd.shape) or tuple(conf.shape) != tuple(rmsd.shape):
+        raise ValueError("select_by_confidence: rmsd, cdis and conf must share one [S, B] shape; got %s, %s, %s"
+                         % (tuple(rmsd.shape), tuple(cdis.shape), tuple(conf.shape)))
+    if not 1 <= int(top_n) <= rmsd.shape[0]:
+        raise ValueError("select_by_confidence: top_n must be in [1, S = %d]; got %r" % (rmsd.shape[0], top_n))
+    pick = torch.argsort(conf, dim=0, descending=True, stable=True)[:int(top_n)]
+    return rmsd.gather(0, pick).min(0).values, cdis.gather(0, pick).min(0).values
+
+
+def sampling_metrics(rmsd, cdis, conf, top_n=1):
+    """test_sampling_fabind.py:177-191 on the selection above: mean, the < 2 A and < 5 A rates and the quartiles of the selected
+    RMSD and centroid distance.  The rates divide by B (the reference hard-codes its test set's 363).  -> dict of python floats."""
+    r, c = select_by_confidence(rmsd, cdis, conf, top_n)
+    vals, names = [], []
+    for x, p in ((r.double(), "rmsd"), (c.double(), "centroid_dis")):
+        names += [p + s for s in ("_mean", "_2A", "_5A", "_25", "_50", "_75")]
+        vals += [x.mean(), (x < 2).double().mean(), (x < 5).double().mean()] + [torch.quantile(x, q) for q in (0.25, 0.50, 0.75)]
+    return dict(zip(names, torch.stack(vals).tolist()))

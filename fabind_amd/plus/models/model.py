@@ -427,6 +427,41 @@ def compute_loss(out, data, args=None):
                        pocket_radius=rad, pocket_center=cen)
 
 
+def confidence_terms(out, coords_true, mode="logsigmoid", with_ce=False, group_size=None, rmsd=None):
+    """The confidence step's device work on the forward's 7-tuple (csrc/ranking.hip): pose statistics of the DETACHED coordinates, then
+    the ranking loss of the score.  -> (loss, dict(ranking, ce, rmsd, centroid_dis, counts)), all device tensors; no read-back."""
+    from ... import ops
+    if len(out) != 7:
+        raise ValueError("confidence loss: expected the 7-tuple of a model built with args.confidence_training; got %d outputs" % len(out))
+    coords, cb, score = out[0], out[1], out[5]
+    if score.numel() != score.shape[0]:
+        raise ValueError("confidence loss: one score per sample expected; got shape %s" % (tuple(score.shape),))
+    score = score.reshape(-1)
+    B = score.shape[0]
+    plain, cdis = ops.pose_stats(coords, coords_true, cb, B)
+    if rmsd is not None:
+        if rmsd.numel() != B:
+            raise ValueError("confidence loss: rmsd must hold one value per sample (%d); got shape %s" % (B, tuple(rmsd.shape)))
+        plain = rmsd.detach().reshape(-1).to(device=score.device, dtype=torch.float32)
+    loss, ranking, ce, _, counts = ops.rank_loss(score, plain, group_size=group_size, mode=mode, with_ce=with_ce)
+    return loss, dict(ranking=ranking, ce=ce, rmsd=plain, centroid_dis=cdis, counts=counts)
+
+
+def compute_confidence_loss(out, data, args=None, group_size=None, rmsd=None):
+    """FABind+ confidence-training loss (reference utils/training_confidence.py:41-77; validation :215-252) as a function of the
+    forward's 7-tuple under `args.confidence_training`; reads `data.coords` AFTER forward (pocket frame), like compute_loss.
+    The samples of a group are the copies of one complex: within a group the copy with the lower RMSD should score higher
+    (`args.ranking_loss`: logsigmoid / dynamic_hinge), plus with `args.keep_cls_2A` the BCE of the score against [RMSD < 2 A].
+    group_size None: the whole batch is one group (the reference asserts batch_size == 1 with num_copies copies); an integer: every
+    consecutive run of that many samples is ranked on its own and the loss is the mean over the groups.  rmsd: a precomputed [B]
+    vector (e.g. symmetry.symmetric_rmsd) in place of the plain RMSD.  The gradient reaches the score only (the reference
+    detaches the coordinates).  Returns (loss, info): info = ranking, ce (scalars), rmsd, centroid_dis [B], counts int32 [G, 4]
+    (ops.COUNT_NAMES) -- device tensors; the call never waits for the device.  Usable as parallel.train_step's compute_loss."""
+    mode = getattr(args, "ranking_loss", "logsigmoid") if args is not None else "logsigmoid"
+    with_ce = bool(getattr(args, "keep_cls_2A", False)) if args is not None else False
+    return confidence_terms(out, data.coords, mode, with_ce, group_size, rmsd)
+
+
 def get_model(args, logger):
     logger.log_message("FABind plus")
     return FABindPlus(args, args.hidden_size, args.pocket_pred_hidden_size)

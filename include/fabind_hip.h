@@ -74,6 +74,7 @@ const char* fabind_last_error(void);
  *     step with global-norm clip and non-finite skip; fabind_sizeof_args(5) = sizeof(FabindAdamRow)).  Purely additive: no existing entry
  *     point or struct changed, so the version stays.  Likewise fabind_gemm_plan + FB_GEMM_FAM_* (which kernel and epilogue fabind_gemm
  *     selects, reported without a launch).
+ *     Likewise fabind_pose_stats / fabind_rank_loss_fwd (csrc/ranking.hip: FABind+ confidence training).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -461,6 +462,24 @@ int fabind_sym_automorphisms(const int* labels, const int* nbr_ptr, const int* n
 int fabind_sym_score(const float* pred, int n_pose, int n_atoms, const float* ref, const int* atom_off, const int* flat_off,
                      const int* auto_cnt, const int* flat, int n_ligands, int max_atoms, float* min_rmsd, int* arg_rmsd, float* min_sl1,
                      int* arg_sl1, int* best_idx, hipStream_t stream);
+/* FABind+ confidence training (FABind_plus/fabind/utils/training_confidence.py:41-77, :215-252).
+ * fabind_pose_stats: per sample b over the atoms [atom_off[b], atom_off[b + 1]) (atom_off int32 [B + 1]; pred / truth fp32 [n_atoms, 3]):
+ *   rmsd[b] = sqrt(mean_i |p_i - t_i|^2), cdis[b] = |mean_i (p_i - t_i)| (the distance of the two centroids); an empty sample gives
+ *   0 / 0.  One wave per sample, fixed summation order.
+ * fabind_rank_loss_fwd: the pairwise ranking loss of G groups of samples, group g = [group_off[g], group_off[g + 1]) (int32 [G + 1],
+ *   2 <= size S <= 1024: the caller checks; a group outside that range gets NaN terms and zero counts).  b is better than a when
+ *   (rmsd_b, b) < (rmsd_a, a); over the P = S(S-1)/2 pairs, delta = s_better - s_worse:
+ *     mode 0 (logsigmoid)    term = max(-delta, 0) + log1p(exp(-|delta|))
+ *     mode 1 (dynamic_hinge) term = relu((rmsd_worse - rmsd_better) - delta)
+ *   ranking = sum / P; ce = mean_a BCE-with-logits(s_a, [rmsd_a < 2]) if with_ce else 0.
+ *   terms fp32 [G, 3] = (ranking, ce, ranking + ce); d_scores fp32 [n_samples] = d (ranking + ce) / d s_a (relu' = 0 at 0);
+ *   counts int32 [G, 4] = (#pairs with s_better > s_worse, P, [score of the best sample > every other score],
+ *   #{a : [s_first > 0] == [rmsd_a < 2]} with s_first the group's first sample, as the reference's line 77 computes it).
+ *   One work-group per group; fixed-order sums, no atomics, no state between launches: bit-reproducible.
+ * Backward-compatible additions under ABI 19. */
+int fabind_pose_stats(const float* pred, const float* truth, const int* atom_off, int B, float* rmsd, float* cdis, hipStream_t stream);
+int fabind_rank_loss_fwd(const float* scores, const float* rmsd, const int* group_off, int G, int mode, int with_ce, float* terms,
+                         float* d_scores, int* counts, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross attention (RowAttentionBlock / Attention._attention, models/cross_att.py:118-134,

@@ -18,6 +18,13 @@ ACT_NONE, ACT_SILU, ACT_RELU, ACT_SIGMOID, ACT_STORED_DERIV = 0, 1, 2, 3, 4
 # FB_GEMM_FAM_*: the kernel family fabind_gemm_plan reports
 GEMM_FAM_NT_F32, GEMM_FAM_NT_F32_BF16, GEMM_FAM_NT_BF16, GEMM_FAM_GLDS, GEMM_FAM_PIPE, GEMM_FAM_X3, GEMM_FAM_X3_PRO, GEMM_FAM_PERSIST = range(8)
 
+# form ids of the normalisation launchers (FB_LNR_* / FB_LNB_* / FB_RST_* / FB_ELF_* / FB_ELB_* of include/fabind_hip.h)
+LNR_8S16, LNR_8S32, LNR_V8_1, LNR_V8_2, LNR_V8_3, LNR_V8_4, LNR_S2, LNR_S8, LNR_S16, LNR_S32, LNR_COUNT = range(11)
+LNB_8S16, LNB_8S32, LNB_V8_1, LNB_V8_2, LNB_V8_3, LNB_S2, LNB_S8, LNB_S16, LNB_S20, LNB_S32, LNB_COUNT = range(11)
+RST_BF16_1, RST_BF16_2, RST_BF16_4, RST_GENERIC, RST_COUNT = range(5)
+ELF_WAVE1, ELF_WAVE1_TAIL, ELF_WAVE2_TAIL, ELF_CHUNK, ELF_COUNT = range(5)
+ELB_NPL1, ELB_NPL2, ELB_NPL3, ELB_COUNT = range(4)
+
 _vp, _i, _f, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_long
 
 
@@ -99,6 +106,14 @@ SIGNATURES = {
     "fabind_edge_lnfold": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _vp, _f, ctypes.c_uint, _vp],
     "fabind_edge_lnfold_bwd_blocks": [_i],
     "fabind_edge_lnfold_bwd": [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _i, _vp],
+    # the form report of csrc/norm.hip: host functions, nothing is launched, no stream
+    "fabind_layernorm_rows_form": [_vp, _i, _i, _vp, _i, _i],
+    "fabind_layernorm_rows_bwd_form": [_vp, _i, _vp, _i, _vp, _i, _i],
+    "fabind_row_stats_form": [_vp, _i, _i, _i],
+    "fabind_edge_lnfold_form": [_i, _i, ctypes.POINTER(_i)],
+    "fabind_edge_lnfold_blocks": [_i],
+    "fabind_edge_lnfold_bwd_form": [_i, ctypes.POINTER(_i)],
+    "fabind_inter_coord_fold_blocks": [_i],
     "fabind_inter_coord_fold": [_vp, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _vp, _f, ctypes.c_uint, _vp],
     "fabind_post_optimize": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
     "fabind_sym_automorphisms": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],

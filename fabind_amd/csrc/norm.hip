@@ -233,35 +233,34 @@ static bool ln_vec8_ok(const void* x, int ldx, int C, const void* y, int ldy, in
     const int C8 = (C + 7) / 8 * 8;
     return ldx % 8 == 0 && ldy % 8 == 0 && pad_to % 8 == 0 && ldx >= C8 && pad_to >= C8 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)y) & 15) == 0;
 }
+// which kernel fabind_layernorm_rows launches (FB_LNR_* of fabind_hip.h); launches nothing
+extern "C" int fabind_layernorm_rows_form(const void* x, int ldx, int C, const void* y, int ldy, int pad_to) {
+    if (ln_vec8_ok(x, ldx, C, y, ldy, pad_to)) {
+        if (C <= 128) return FB_LNR_8S16;
+        if (C <= 256) return FB_LNR_8S32;
+        return C <= 512 ? FB_LNR_V8_1 : C <= 1024 ? FB_LNR_V8_2 : C <= 1536 ? FB_LNR_V8_3 : FB_LNR_V8_4;
+    }
+    return C <= 128 ? FB_LNR_S2 : C <= 512 ? FB_LNR_S8 : C <= 1024 ? FB_LNR_S16 : FB_LNR_S32;
+}
 extern "C" int fabind_layernorm_rows(const void* x, int x_dt, int ldx, const float* w, const float* b, float eps, int R, int C,
                                      void* y, int y_dt, int ldy, int pad_to, hipStream_t stream) {
     if (R <= 0) return 0;
     FB_REQUIRE(pad_to <= ldy && C <= ldx, "fabind_layernorm_rows: pad_to <= ldy, C <= ldx");
     FB_REQUIRE(C <= 2048, "fabind_layernorm_rows: C <= 2048");
-    if (ln_vec8_ok(x, ldx, C, y, ldy, pad_to) && C <= 256) {
-        if (C <= 128)
-            hipLaunchKernelGGL((layernorm_rows8s_kernel<16>), dim3((R + 15) / 16), dim3(256), 0, stream, x, x_dt, ldx, w, b, eps, R, C, y, y_dt,
-                               ldy, pad_to);
-        else
-            hipLaunchKernelGGL((layernorm_rows8s_kernel<32>), dim3((R + 7) / 8), dim3(256), 0, stream, x, x_dt, ldx, w, b, eps, R, C, y, y_dt,
-                               ldy, pad_to);
-        FB_CHECK_LAUNCH();
-        return 0;
+#define LNR_LAUNCH(KERNEL_, ROWS_) hipLaunchKernelGGL((KERNEL_), dim3((R + ROWS_ - 1) / ROWS_), dim3(256), 0, stream, x, x_dt, ldx, \
+                                                      w, b, eps, R, C, y, y_dt, ldy, pad_to)
+    switch (fabind_layernorm_rows_form(x, ldx, C, y, ldy, pad_to)) {
+        case FB_LNR_8S16: LNR_LAUNCH(layernorm_rows8s_kernel<16>, 16); break;
+        case FB_LNR_8S32: LNR_LAUNCH(layernorm_rows8s_kernel<32>, 8); break;
+        case FB_LNR_V8_1: LNR_LAUNCH(layernorm_rows8_kernel<1>, 4); break;
+        case FB_LNR_V8_2: LNR_LAUNCH(layernorm_rows8_kernel<2>, 4); break;
+        case FB_LNR_V8_3: LNR_LAUNCH(layernorm_rows8_kernel<3>, 4); break;
+        case FB_LNR_V8_4: LNR_LAUNCH(layernorm_rows8_kernel<4>, 4); break;
+        case FB_LNR_S2: LNR_LAUNCH(layernorm_rows_kernel<2>, 4); break;
+        case FB_LNR_S8: LNR_LAUNCH(layernorm_rows_kernel<8>, 4); break;
+        case FB_LNR_S16: LNR_LAUNCH(layernorm_rows_kernel<16>, 4); break;
+        default: LNR_LAUNCH(layernorm_rows_kernel<32>, 4); break;
     }
-    if (ln_vec8_ok(x, ldx, C, y, ldy, pad_to)) {
-#define LNR8_LAUNCH(NCH_) hipLaunchKernelGGL((layernorm_rows8_kernel<NCH_>), dim3((R + 3) / 4), dim3(256), 0, stream, x, x_dt, ldx, \
-                                             w, b, eps, R, C, y, y_dt, ldy, pad_to)
-        if (C <= 512) LNR8_LAUNCH(1); else if (C <= 1024) LNR8_LAUNCH(2); else if (C <= 1536) LNR8_LAUNCH(3); else LNR8_LAUNCH(4);
-#undef LNR8_LAUNCH
-        FB_CHECK_LAUNCH();
-        return 0;
-    }
-#define LNR_LAUNCH(NPL_) hipLaunchKernelGGL((layernorm_rows_kernel<NPL_>), dim3((R + 3) / 4), dim3(256), 0, stream, x, x_dt, ldx, \
-                                            w, b, eps, R, C, y, y_dt, ldy, pad_to)
-    if (C <= 128) LNR_LAUNCH(2);
-    else if (C <= 512) LNR_LAUNCH(8);
-    else if (C <= 1024) LNR_LAUNCH(16);
-    else LNR_LAUNCH(32);
 #undef LNR_LAUNCH
     FB_CHECK_LAUNCH();
     return 0;
@@ -318,18 +317,22 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const void* __restrict__
     q = wave_sum(q);
     if (lane == 0) { mu[r] = m; rs[r] = rsqrtf(q / (float)C + eps); }
 }
+// which kernel fabind_row_stats launches (FB_RST_* of fabind_hip.h); launches nothing
+extern "C" int fabind_row_stats_form(const void* x, int x_dt, int ldx, int C) {
+    if (x_dt == FB_DT_BF16 && C % 8 == 0 && ldx % 8 == 0 && C <= 2048 && (((uintptr_t)x) & 15) == 0)
+        return C <= 512 ? FB_RST_BF16_1 : C <= 1024 ? FB_RST_BF16_2 : FB_RST_BF16_4;
+    return FB_RST_GENERIC;
+}
 extern "C" int fabind_row_stats(const void* x, int x_dt, int ldx, float eps, int R, int C, float* mu, float* rs,
                                 hipStream_t stream) {
     if (R <= 0) return 0;
-    if (x_dt == FB_DT_BF16 && C % 8 == 0 && ldx % 8 == 0 && C <= 2048 && (((uintptr_t)x) & 15) == 0) {
-        const dim3 grid((R + 3) / 4);
-        if (C <= 512) hipLaunchKernelGGL(row_stats_bf16_kernel<1>, grid, dim3(256), 0, stream, (const bf16_t*)x, ldx, eps, R, C, mu, rs);
-        else if (C <= 1024) hipLaunchKernelGGL(row_stats_bf16_kernel<2>, grid, dim3(256), 0, stream, (const bf16_t*)x, ldx, eps, R, C, mu, rs);
-        else hipLaunchKernelGGL(row_stats_bf16_kernel<4>, grid, dim3(256), 0, stream, (const bf16_t*)x, ldx, eps, R, C, mu, rs);
-        FB_CHECK_LAUNCH();
-        return 0;
+    const dim3 grid((R + 3) / 4);
+    switch (fabind_row_stats_form(x, x_dt, ldx, C)) {
+        case FB_RST_BF16_1: hipLaunchKernelGGL(row_stats_bf16_kernel<1>, grid, dim3(256), 0, stream, (const bf16_t*)x, ldx, eps, R, C, mu, rs); break;
+        case FB_RST_BF16_2: hipLaunchKernelGGL(row_stats_bf16_kernel<2>, grid, dim3(256), 0, stream, (const bf16_t*)x, ldx, eps, R, C, mu, rs); break;
+        case FB_RST_BF16_4: hipLaunchKernelGGL(row_stats_bf16_kernel<4>, grid, dim3(256), 0, stream, (const bf16_t*)x, ldx, eps, R, C, mu, rs); break;
+        default: hipLaunchKernelGGL(row_stats_kernel, grid, dim3(256), 0, stream, x, x_dt, ldx, eps, R, C, mu, rs); break;
     }
-    hipLaunchKernelGGL(row_stats_kernel, dim3((R + 3) / 4), dim3(256), 0, stream, x, x_dt, ldx, eps, R, C, mu, rs);
     FB_CHECK_LAUNCH();
     return 0;
 }
@@ -521,6 +524,24 @@ __global__ __launch_bounds__(256) void edge_lnfold_wave_kernel(const bf16_t* __r
         }
     }
 }
+#ifndef ELF_WAVE_MIN_H
+#define ELF_WAVE_MIN_H 0
+#endif
+// which kernel fabind_edge_lnfold launches (FB_ELF_* of fabind_hip.h) and the edges a wave takes per trip of its walk (0: the
+// per-chunk kernel does not walk); launches nothing.  fabind_edge_lnfold_blocks: the capped grid of the wave forms.
+extern "C" int fabind_edge_lnfold_form(int Kp, int H, int* edges_per_trip) {
+    int form = FB_ELF_CHUNK, u = 0;
+    if (H % 4 == 0 && H <= 512 && H >= ELF_WAVE_MIN_H && Kp / 8 - H / 4 <= 64) {
+        if (H > 256) { form = FB_ELF_WAVE2_TAIL; u = ELF_U2; }
+        else if (Kp / 8 > 64) { form = FB_ELF_WAVE1_TAIL; u = ELF_U1; }
+        else { form = FB_ELF_WAVE1; u = ELF_U1; }       // every chunk of the row in one pass (H <= 128)
+    }
+    if (edges_per_trip) *edges_per_trip = u;
+    return form;
+}
+// the forward walks (edge_lnfold's wave forms, inter_coord_fold): four waves per work-group, at most 2048 work-groups
+static int fold_fwd_blocks(int E) { return (int)std::min<size_t>(((size_t)E + 3) / 4, (size_t)256 * 8); }
+extern "C" int fabind_edge_lnfold_blocks(int E) { return fold_fwd_blocks(E); }
 extern "C" int fabind_edge_lnfold(const void* AB, int ldab, int Kp, int H, const int* row, const int* col, const float* rho,
                                   const float* stat, float eps, const float* w_r, const float* c_r, const float* c_c,
                                   const float* dvec, int E, void* out, float p_drop, unsigned seed, hipStream_t stream) {
@@ -529,24 +550,21 @@ extern "C" int fabind_edge_lnfold(const void* AB, int ldab, int Kp, int H, const
     FB_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "fabind_edge_lnfold: p_drop in [0, 1)");
     const uint32_t thr = (uint32_t)(p_drop * 65536.0f + 0.5f);
     const float dscale = 1.0f / (1.0f - (float)thr / 65536.0f);
-#ifndef ELF_WAVE_MIN_H
-#define ELF_WAVE_MIN_H 0
-#endif
-    if (H % 4 == 0 && H <= 512 && H >= ELF_WAVE_MIN_H && Kp / 8 - H / 4 <= 64) {
-        const int blocks = (int)std::min<size_t>(((size_t)E + 3) / 4, (size_t)256 * 8);
-#define ELF_LAUNCH(NN, UU, TT)                                                                                                      \
-        hipLaunchKernelGGL((edge_lnfold_wave_kernel<NN, UU, TT>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)AB, ldab, Kp, H, row, \
-                           col, rho, (const float2*)stat, eps, w_r, c_r, c_c, dvec, E, (bf16_t*)out, thr, dscale, (uint32_t)seed)
-        if (H > 256) ELF_LAUNCH(2, ELF_U2, true);
-        else if (Kp / 8 > 64) ELF_LAUNCH(1, ELF_U1, true);
-        else ELF_LAUNCH(1, ELF_U1, false);              // every chunk of the row in one pass (H <= 128)
-#undef ELF_LAUNCH
-        FB_CHECK_LAUNCH();
-        return 0;
-    }
+    const int blocks = fabind_edge_lnfold_blocks(E);
     const size_t total = (size_t)E * (Kp / 8);
-    hipLaunchKernelGGL(edge_lnfold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)AB, ldab, Kp,
-                       H, row, col, rho, (const float2*)stat, eps, w_r, c_r, c_c, dvec, E, (bf16_t*)out, thr, dscale, (uint32_t)seed);
+#define ELF_LAUNCH(NN, UU, TT)                                                                                                      \
+    hipLaunchKernelGGL((edge_lnfold_wave_kernel<NN, UU, TT>), dim3(blocks), dim3(256), 0, stream, (const bf16_t*)AB, ldab, Kp, H, row, \
+                       col, rho, (const float2*)stat, eps, w_r, c_r, c_c, dvec, E, (bf16_t*)out, thr, dscale, (uint32_t)seed)
+    switch (fabind_edge_lnfold_form(Kp, H, nullptr)) {
+        case FB_ELF_WAVE2_TAIL: ELF_LAUNCH(2, ELF_U2, true); break;
+        case FB_ELF_WAVE1_TAIL: ELF_LAUNCH(1, ELF_U1, true); break;
+        case FB_ELF_WAVE1: ELF_LAUNCH(1, ELF_U1, false); break;
+        default:
+            hipLaunchKernelGGL(edge_lnfold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)AB, ldab, Kp,
+                               H, row, col, rho, (const float2*)stat, eps, w_r, c_r, c_c, dvec, E, (bf16_t*)out, thr, dscale, (uint32_t)seed);
+            break;
+    }
+#undef ELF_LAUNCH
     FB_CHECK_LAUNCH();
     return 0;
 }
@@ -684,6 +702,13 @@ __global__ __launch_bounds__(256, ELB_MINW) void edge_lnfold_bwd_kernel(const bf
         part[(size_t)blockIdx.x * 4 * Kp + i] = ((sred[i] + sred[4 * Kp + i]) + sred[8 * Kp + i]) + sred[12 * Kp + i];
 }
 extern "C" int fabind_edge_lnfold_bwd_blocks(int E) { return (int)std::min<size_t>(((size_t)E + 3) / 4, (size_t)256 * 4); }
+// which kernel fabind_edge_lnfold_bwd launches (FB_ELB_* of fabind_hip.h) and the edges a wave takes per trip of its walk; launches nothing
+extern "C" int fabind_edge_lnfold_bwd_form(int Kp, int* edges_per_trip) {
+    const int npl = (Kp / 8 + 63) / 64;
+    const int form = npl <= 1 ? FB_ELB_NPL1 : npl == 2 ? FB_ELB_NPL2 : FB_ELB_NPL3;
+    if (edges_per_trip) *edges_per_trip = form == FB_ELB_NPL1 ? ELB_U1 : form == FB_ELB_NPL2 ? ELB_U2 : ELB_U3;
+    return form;
+}
 extern "C" int fabind_edge_lnfold_bwd(const void* AB, int ldab, int Kp, int H, const int* row, const int* col, const float* rho,
                                       const float* stat, float eps, const float* w_r, const float* c_r, const float* c_c,
                                       const void* out, const void* dout, int E, float p_drop, void* du, float* es,
@@ -694,7 +719,6 @@ extern "C" int fabind_edge_lnfold_bwd(const void* AB, int ldab, int Kp, int H, c
     const uint32_t thr = (uint32_t)(p_drop * 65536.0f + 0.5f);
     const float dscale = 1.0f / (1.0f - (float)thr / 65536.0f);
     const size_t lds = (size_t)16 * Kp * sizeof(float);
-    const int npl = (Kp / 8 + 63) / 64;
 #define ELB_LAUNCH(NN, UU)                                                                                                             \
     do {                                                                                                                           \
         /* the attribute is per DEVICE and must cover the instantiation's LARGEST request (NN x 512 columns: 16 x NN x 512 x 4 bytes), not the \
@@ -710,7 +734,11 @@ extern "C" int fabind_edge_lnfold_bwd(const void* AB, int ldab, int Kp, int H, c
                            (const float2*)stat, eps, w_r, c_r, c_c, (const bf16_t*)out, (const bf16_t*)dout, E, dscale, (bf16_t*)du,  \
                            (float4*)es, drho, part);                                                                                \
     } while (0)
-    if (npl <= 1) ELB_LAUNCH(1, ELB_U1); else if (npl == 2) ELB_LAUNCH(2, ELB_U2); else ELB_LAUNCH(3, ELB_U3);
+    switch (fabind_edge_lnfold_bwd_form(Kp, nullptr)) {
+        case FB_ELB_NPL1: ELB_LAUNCH(1, ELB_U1); break;
+        case FB_ELB_NPL2: ELB_LAUNCH(2, ELB_U2); break;
+        default: ELB_LAUNCH(3, ELB_U3); break;
+    }
 #undef ELB_LAUNCH
     FB_CHECK_LAUNCH();
     return 0;
@@ -757,6 +785,8 @@ __global__ __launch_bounds__(256) void inter_coord_fold_kernel(const bf16_t* __r
         if (lane == 0) s_out[e] = acc;
     }
 }
+// the capped grid of fabind_inter_coord_fold: four waves per work-group, one edge per wave and trip
+extern "C" int fabind_inter_coord_fold_blocks(int E) { return fold_fwd_blocks(E); }
 extern "C" int fabind_inter_coord_fold(const void* P, int ldp, int H, const int* col, const float* rho, const float* stat,
                                        float q_w, float eps, const float* u, const float* d, const float* w3, int E,
                                        float* s_out, float p_drop, unsigned seed, hipStream_t stream) {
@@ -765,7 +795,7 @@ extern "C" int fabind_inter_coord_fold(const void* P, int ldp, int H, const int*
     FB_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "fabind_inter_coord_fold: p_drop in [0, 1)");
     const uint32_t thr = (uint32_t)(p_drop * 65536.0f + 0.5f);
     const float dscale = 1.0f / (1.0f - (float)thr / 65536.0f);
-    const int blocks = (int)std::min<size_t>(((size_t)E + 3) / 4, (size_t)256 * 8);
+    const int blocks = fabind_inter_coord_fold_blocks(E);
     hipLaunchKernelGGL(inter_coord_fold_kernel, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)P, ldp, H, col, rho,
                        (const float2*)stat, q_w, eps, u, d, w3, E, s_out, thr, dscale, (uint32_t)seed);
     FB_CHECK_LAUNCH();
@@ -1006,6 +1036,21 @@ __global__ __launch_bounds__(256) void layernorm_rows_bwd8s_kernel(const void* _
         dbp[(size_t)blockIdx.x * C + c] = sh[C + c];
     }
 }
+// which kernel fabind_layernorm_rows_bwd launches (FB_LNB_* of fabind_hip.h); launches nothing
+extern "C" int fabind_layernorm_rows_bwd_form(const void* x, int ldx, const void* dy, int lddy, const void* dx, int lddx, int C) {
+    const int C8 = (C + 7) / 8 * 8;
+    if (ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldx >= C8 && lddy >= C8 && lddx >= C8 && (((uintptr_t)x) & 15) == 0 &&
+        (((uintptr_t)dy) & 15) == 0 && (((uintptr_t)dx) & 15) == 0 && C <= 1536) {
+        if (C <= 128) return FB_LNB_8S16;
+        if (C <= 256) return FB_LNB_8S32;
+        return C <= 512 ? FB_LNB_V8_1 : C <= 1024 ? FB_LNB_V8_2 : FB_LNB_V8_3;
+    }
+    if (C <= 128) return FB_LNB_S2;
+    if (C <= 512) return FB_LNB_S8;
+    if (C <= 1024) return FB_LNB_S16;
+    if (C <= 1280) return FB_LNB_S20;   /* the FABind+ edge input (2H + 1 = 1025 padded to 1088 at H = 512): 32 column sets per lane left one wave per SIMD */
+    return FB_LNB_S32;
+}
 extern "C" int fabind_layernorm_rows_bwd(const void* x, int x_dt, int ldx, const float* w, const void* dy, int dy_dt, int lddy,
                                          float eps, int R, int C, void* dx, int dx_dt, int lddx, float* dw_part, float* db_part,
                                          int nblk, hipStream_t stream) {
@@ -1013,33 +1058,20 @@ extern "C" int fabind_layernorm_rows_bwd(const void* x, int x_dt, int ldx, const
     FB_REQUIRE(C <= 2048, "fabind_layernorm_rows_bwd: C <= 2048");
     FB_REQUIRE(nblk >= 1, "fabind_layernorm_rows_bwd: nblk >= 1 (rows of the dw / db partial buffers)");
     const size_t lds = (size_t)2 * C * sizeof(float);
-    const int C8 = (C + 7) / 8 * 8;
-    if (ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldx >= C8 && lddy >= C8 && lddx >= C8 && (((uintptr_t)x) & 15) == 0 &&
-        (((uintptr_t)dy) & 15) == 0 && (((uintptr_t)dx) & 15) == 0 && C <= 1536) {
-        if (C <= 256) {
-            if (C <= 128)
-                hipLaunchKernelGGL((layernorm_rows_bwd8s_kernel<16>), dim3(nblk), dim3(256), lds, stream, x, x_dt, ldx, w, dy, dy_dt, lddy, eps, R,
-                                   C, dx, dx_dt, lddx, dw_part, db_part);
-            else
-                hipLaunchKernelGGL((layernorm_rows_bwd8s_kernel<32>), dim3(nblk), dim3(256), lds, stream, x, x_dt, ldx, w, dy, dy_dt, lddy, eps, R,
-                                   C, dx, dx_dt, lddx, dw_part, db_part);
-            FB_CHECK_LAUNCH();
-            return 0;
-        }
-#define LNB8_LAUNCH(NCH_) hipLaunchKernelGGL((layernorm_rows_bwd8_kernel<NCH_>), dim3(nblk), dim3(256), lds, stream, x, x_dt, ldx, w, dy, \
-                                             dy_dt, lddy, eps, R, C, dx, dx_dt, lddx, dw_part, db_part)
-        if (C <= 512) LNB8_LAUNCH(1); else if (C <= 1024) LNB8_LAUNCH(2); else LNB8_LAUNCH(3);
-#undef LNB8_LAUNCH
-        FB_CHECK_LAUNCH();
-        return 0;
+#define LNB_LAUNCH(KERNEL_) hipLaunchKernelGGL((KERNEL_), dim3(nblk), dim3(256), lds, stream, x, x_dt, ldx, w, dy, dy_dt, lddy, eps, R, \
+                                               C, dx, dx_dt, lddx, dw_part, db_part)
+    switch (fabind_layernorm_rows_bwd_form(x, ldx, dy, lddy, dx, lddx, C)) {
+        case FB_LNB_8S16: LNB_LAUNCH(layernorm_rows_bwd8s_kernel<16>); break;
+        case FB_LNB_8S32: LNB_LAUNCH(layernorm_rows_bwd8s_kernel<32>); break;
+        case FB_LNB_V8_1: LNB_LAUNCH(layernorm_rows_bwd8_kernel<1>); break;
+        case FB_LNB_V8_2: LNB_LAUNCH(layernorm_rows_bwd8_kernel<2>); break;
+        case FB_LNB_V8_3: LNB_LAUNCH(layernorm_rows_bwd8_kernel<3>); break;
+        case FB_LNB_S2: LNB_LAUNCH(layernorm_rows_bwd_kernel<2>); break;
+        case FB_LNB_S8: LNB_LAUNCH(layernorm_rows_bwd_kernel<8>); break;
+        case FB_LNB_S16: LNB_LAUNCH(layernorm_rows_bwd_kernel<16>); break;
+        case FB_LNB_S20: LNB_LAUNCH(layernorm_rows_bwd_kernel<20>); break;
+        default: LNB_LAUNCH(layernorm_rows_bwd_kernel<32>); break;
     }
-#define LNB_LAUNCH(NPL_) hipLaunchKernelGGL((layernorm_rows_bwd_kernel<NPL_>), dim3(nblk), dim3(256), lds, stream, x, x_dt, \
-                                            ldx, w, dy, dy_dt, lddy, eps, R, C, dx, dx_dt, lddx, dw_part, db_part)
-    if (C <= 128) LNB_LAUNCH(2);
-    else if (C <= 512) LNB_LAUNCH(8);
-    else if (C <= 1024) LNB_LAUNCH(16);
-    else if (C <= 1280) LNB_LAUNCH(20);   /* the FABind+ edge input (2H + 1 = 1025 padded to 1088 at H = 512): 32 column sets per lane left one wave per SIMD */
-    else LNB_LAUNCH(32);
 #undef LNB_LAUNCH
     FB_CHECK_LAUNCH();
     return 0;

@@ -723,6 +723,44 @@ def row_stats(x, eps):
     return mu, rs
 
 
+# the form report of csrc/norm.hip (include/fabind_hip.h: FB_LNR_* ...): which kernel a call would launch; nothing is launched
+def layernorm_rows_form(x, out, C=None, pad_to=None):
+    """Form of layernorm_rows for input x [R, >= C] writing out [R, pad_to]  ->  _lib.LNR_*."""
+    C = x.shape[1] if C is None else C
+    pad_to = out.shape[1] if pad_to is None else pad_to
+    return int(_lib.load().fabind_layernorm_rows_form(ptr(x), _ld(x), C, ptr(out), _ld(out), pad_to))
+
+
+def layernorm_rows_bwd_form(x, dy, dx, C=None):
+    """Form of fabind_layernorm_rows_bwd for the three row buffers  ->  _lib.LNB_*."""
+    C = x.shape[1] if C is None else C
+    return int(_lib.load().fabind_layernorm_rows_bwd_form(ptr(x), _ld(x), ptr(dy), _ld(dy), ptr(dx), _ld(dx), C))
+
+
+def row_stats_form(x):
+    """Form of row_stats  ->  _lib.RST_*."""
+    return int(_lib.load().fabind_row_stats_form(ptr(x), dt_code(x.dtype), _ld(x), x.shape[1]))
+
+
+def edge_lnfold_form(Kp, H):
+    """(form _lib.ELF_*, edges per wave and trip, the grid's cap in work-groups of four waves) of edge_lnfold."""
+    u = ctypes.c_int(0)
+    lib = _lib.load()
+    return int(lib.fabind_edge_lnfold_form(Kp, H, ctypes.byref(u))), u.value, int(lib.fabind_edge_lnfold_blocks(2 ** 31 - 1))
+
+
+def edge_lnfold_bwd_form(Kp):
+    """(form _lib.ELB_*, edges per wave and trip, the grid's cap in work-groups of four waves) of edge_lnfold_bwd."""
+    u = ctypes.c_int(0)
+    lib = _lib.load()
+    return int(lib.fabind_edge_lnfold_bwd_form(Kp, ctypes.byref(u))), u.value, int(lib.fabind_edge_lnfold_bwd_blocks(2 ** 31 - 1))
+
+
+def inter_coord_fold_blocks(E=2 ** 31 - 1):
+    """Work-groups (four waves, one edge per wave and trip) inter_coord_fold launches for E edges; the default asks for the cap."""
+    return int(_lib.load().fabind_inter_coord_fold_blocks(E))
+
+
 def pair_update_fused(T, b_off, p_node, c_node, z, Wop, bo, ln_w, ln_b, eps, W1p, b1, W2p, b2, Wbp=None, bb=None, p_drop=0.0,
                       seed=0):
     """FABind+ pair update for a ragged pair list (csrc/pair_fused.hip): z [pairs,H] bf16 -> (z' bf16, bias' [pairs,16] fp32

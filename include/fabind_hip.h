@@ -75,6 +75,8 @@ const char* fabind_last_error(void);
  *     point or struct changed, so the version stays.  Likewise fabind_gemm_plan + FB_GEMM_FAM_* (which kernel and epilogue fabind_gemm
  *     selects, reported without a launch).
  *     Likewise fabind_pose_stats / fabind_rank_loss_fwd (csrc/ranking.hip: FABind+ confidence training).
+ *     Likewise the form report of csrc/norm.hip (fabind_layernorm_rows_form, _rows_bwd_form, fabind_row_stats_form, fabind_edge_lnfold_form /
+ *     _blocks, fabind_edge_lnfold_bwd_form, fabind_inter_coord_fold_blocks + FB_LNR_* / FB_LNB_* / FB_RST_* / FB_ELF_* / FB_ELB_*).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -722,6 +724,61 @@ int fabind_layernorm_fwd(const float* x, const float* w, const float* b, float e
                          float* rstd, hipStream_t stream);
 int fabind_layernorm_bwd(const float* x, const float* w, const float* dy, const float* mean, const float* rstd, int R,
                          int C, float* dx, float* dw_part, float* db_part, hipStream_t stream);
+
+/* Form report of the normalisation launchers: which kernel and template instantiation a call would run, answered by the same host
+ * function the launcher itself dispatches through, without launching anything (host code only: pointers are looked at for their
+ * alignment and never dereferenced).  Every argument is the launcher's argument of that name.  The *_COUNT values close each list. */
+/* fabind_layernorm_rows.  Rows per work-group: 16 (8S16), 8 (8S32), 4 elsewhere. */
+#define FB_LNR_8S16 0  /* layernorm_rows8s_kernel<16>: 8-column accesses, C <= 128, four rows per wave */
+#define FB_LNR_8S32 1  /* layernorm_rows8s_kernel<32>: 8-column accesses, 128 < C <= 256, two rows per wave */
+#define FB_LNR_V8_1 2  /* layernorm_rows8_kernel<1>:   8-column accesses, 256 < C <= 512 */
+#define FB_LNR_V8_2 3  /* layernorm_rows8_kernel<2>:   512 < C <= 1024 */
+#define FB_LNR_V8_3 4  /* layernorm_rows8_kernel<3>:   1024 < C <= 1536 */
+#define FB_LNR_V8_4 5  /* layernorm_rows8_kernel<4>:   1536 < C <= 2048 */
+#define FB_LNR_S2 6    /* layernorm_rows_kernel<2>:    scalar accesses (a leading dimension, pad_to or an address rules out 8 columns), C <= 128 */
+#define FB_LNR_S8 7    /* layernorm_rows_kernel<8>:    128 < C <= 512 */
+#define FB_LNR_S16 8   /* layernorm_rows_kernel<16>:   512 < C <= 1024 */
+#define FB_LNR_S32 9   /* layernorm_rows_kernel<32>:   1024 < C <= 2048 */
+#define FB_LNR_COUNT 10
+int fabind_layernorm_rows_form(const void* x, int ldx, int C, const void* y, int ldy, int pad_to);
+/* fabind_layernorm_rows_bwd.  Every form strides rows over the caller's nblk work-groups of four waves (8S16: 16 rows per work-group and
+ * trip, 8S32: 8, elsewhere 4). */
+#define FB_LNB_8S16 0  /* layernorm_rows_bwd8s_kernel<16>: 8-column accesses, C <= 128 */
+#define FB_LNB_8S32 1  /* layernorm_rows_bwd8s_kernel<32>: 128 < C <= 256 */
+#define FB_LNB_V8_1 2  /* layernorm_rows_bwd8_kernel<1>:   256 < C <= 512 */
+#define FB_LNB_V8_2 3  /* layernorm_rows_bwd8_kernel<2>:   512 < C <= 1024 */
+#define FB_LNB_V8_3 4  /* layernorm_rows_bwd8_kernel<3>:   1024 < C <= 1536 */
+#define FB_LNB_S2 5    /* layernorm_rows_bwd_kernel<2>:    scalar accesses, C <= 128 */
+#define FB_LNB_S8 6    /* layernorm_rows_bwd_kernel<8>:    128 < C <= 512 */
+#define FB_LNB_S16 7   /* layernorm_rows_bwd_kernel<16>:   512 < C <= 1024 */
+#define FB_LNB_S20 8   /* layernorm_rows_bwd_kernel<20>:   1024 < C <= 1280 */
+#define FB_LNB_S32 9   /* layernorm_rows_bwd_kernel<32>:   1280 < C <= 2048 (also every 8-column-capable shape beyond C = 1536) */
+#define FB_LNB_COUNT 10
+int fabind_layernorm_rows_bwd_form(const void* x, int ldx, const void* dy, int lddy, const void* dx, int lddx, int C);
+/* fabind_row_stats */
+#define FB_RST_BF16_1 0   /* row_stats_bf16_kernel<1>: bf16 rows, C % 8 == 0, 16-byte aligned, C <= 512 */
+#define FB_RST_BF16_2 1   /* row_stats_bf16_kernel<2>: 512 < C <= 1024 */
+#define FB_RST_BF16_4 2   /* row_stats_bf16_kernel<4>: 1024 < C <= 2048 */
+#define FB_RST_GENERIC 3  /* row_stats_kernel: every other dtype / shape, two element-wise passes */
+#define FB_RST_COUNT 4
+int fabind_row_stats_form(const void* x, int x_dt, int ldx, int C);
+/* fabind_edge_lnfold.  *edges_per_trip (may be NULL) receives U, the edges a wave takes per trip of its walk over the
+ * 4 x fabind_edge_lnfold_blocks(E) waves of the grid (0 for the per-chunk kernel, which does not walk). */
+#define FB_ELF_WAVE1 0       /* edge_lnfold_wave_kernel<1, ELF_U1, false>: H % 4 == 0, Kp / 8 <= 64: every chunk of the row in one pass */
+#define FB_ELF_WAVE1_TAIL 1  /* edge_lnfold_wave_kernel<1, ELF_U1, true>:  H <= 256, Kp / 8 > 64: 2H leading columns + a tail pass */
+#define FB_ELF_WAVE2_TAIL 2  /* edge_lnfold_wave_kernel<2, ELF_U2, true>:  256 < H <= 512 */
+#define FB_ELF_CHUNK 3       /* edge_lnfold_kernel: one thread per (edge, 8-column chunk): H % 4 != 0, H > 512 or a tail beyond 64 chunks */
+#define FB_ELF_COUNT 4
+int fabind_edge_lnfold_form(int Kp, int H, int* edges_per_trip);
+int fabind_edge_lnfold_blocks(int E);
+/* fabind_edge_lnfold_bwd (grid: fabind_edge_lnfold_bwd_blocks(E) work-groups of four waves) */
+#define FB_ELB_NPL1 0  /* edge_lnfold_bwd_kernel<1, ELB_U1>: Kp <= 512 */
+#define FB_ELB_NPL2 1  /* edge_lnfold_bwd_kernel<2, ELB_U2>: 512 < Kp <= 1024 */
+#define FB_ELB_NPL3 2  /* edge_lnfold_bwd_kernel<3, ELB_U3>: 1024 < Kp <= 1536 */
+#define FB_ELB_COUNT 3
+int fabind_edge_lnfold_bwd_form(int Kp, int* edges_per_trip);
+/* grid of fabind_inter_coord_fold: four waves per work-group, one edge per wave and trip */
+int fabind_inter_coord_fold_blocks(int E);
 
 /* elementwise: out = a + b (fp32), n elements */
 int fabind_add(const float* a, const float* b, float* out, long n, hipStream_t stream);

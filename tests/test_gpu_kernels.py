@@ -557,13 +557,8 @@ def test_inter_coord_fold_matches_layernorm_mlp(H, E, p_drop):
     s = K.inter_coord_fold(d((Vc @ W1w.T).bfloat16()), H, d(col), d(rho), d(stat), float((wc * wc).sum()), 1e-5, d(W1w @ wc),
                            d(W1 @ lb + b1), d(w3), p_drop, seed).cpu()
     if p_drop > 0:
-        thr = int(p_drop * 65536.0 + 0.5)
-        e = torch.arange(E, dtype=torch.int64)[:, None]; c = torch.arange(H, dtype=torch.int64)[None, :]
-        x = (seed + e * H + c) & 0xFFFFFFFF
-        x = x ^ (x >> 16); x = (x * 0x7feb352d) & 0xFFFFFFFF
-        x = x ^ (x >> 15); x = (x * 0x846ca68b) & 0xFFFFFFFF
-        x = x ^ (x >> 16)
-        act = act * ((x & 0xFFFF) >= thr).float() / (1.0 - thr / 65536.0)
+        import norm_refs as NR                                              # the counter-based mask, restated once for all tests
+        act = act * NR.drop_keep(seed, E, H, p_drop).float() / (1.0 - NR.drop_thr(p_drop) / 65536.0)
     ref = act @ w3
     assert (s - ref).abs().max() <= 3e-2 * max(1.0, float(ref.abs().max()))
     assert (s - ref).abs().mean() <= 5e-3 * max(1.0, float(ref.abs().mean()))

@@ -116,6 +116,8 @@ SIGNATURES = {
     "fabind_inter_coord_fold_blocks": [_i],
     "fabind_inter_coord_fold": [_vp, _i, _i, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _vp, _f, ctypes.c_uint, _vp],
     "fabind_post_optimize": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
+    "fabind_distmap_generate": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _l, _i, _i, _i, _i,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_sym_automorphisms": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_sym_score": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_pose_stats": [_vp, _vp, _vp, _i, _vp, _vp, _vp],

@@ -440,6 +440,33 @@ int fabind_post_optimize(const float* x0, const float* ref, const int* atom_off,
                          int n_ligands, int max_atoms, int all_pairs, int steps, float lr, float* x_out, float* loss_out,
                          float* rmsd_out, hipStream_t stream);
 
+/* Ligand poses from a predicted distance map (FABind/fabind/utils/generation_utils.py:42-120): `epochs` Adam iterations (lr, betas
+ * 0.9 / 0.999, eps 1e-8) on the start coordinates x0 of n_repeat starts of a BATCH of ligands in one launch (one work-group per
+ * (ligand, repeat), all epochs inside the kernel).  With dis = min(|p_i - x_k|, 10) and r = dis - y_pred[i, k], at 0-based epoch t
+ *   interaction   = sum |r| (mode 0) | sum r^2 (mode 1) | sum (|r| + 1e-5)^0.5 (mode 2)
+ *   configuration = sum over the listed ordered pairs (k,j) of | |x_k-x_j| - D_kj |  + (excluded_volume ? 2 sum_{k,j} relu(1.22 - |x_k-x_j|) : 0)
+ *   loss          = interaction (t < config_start), else interaction + config_rate (t - config_start) configuration.
+ * x0, x_out: fp32 [n_repeat, n_atoms, 3]; truth fp32 [n_atoms, 3] (the pose the RMSD is taken to); atom_off int32 [n_ligands + 1];
+ * pocket fp32 [sum residues, 3] with pocket_off int32 [n_ligands + 1]; y_pred fp32 flat, ligand l at y_off[l] (int64 [n_ligands]) as
+ * [residues_l, atoms_l] with the atom index fastest (the layout of the model's distance head).  con_ptr int32 [n_atoms + 1] /
+ * con_idx int32 (GLOBAL atom ids) / con_d fp32: for every listed ordered pair (k,j) the list of k holds (j, D_kj) and the list of j
+ * holds (k, D_kj); each entry weighs 1/2 in the loss and 1 in its owner's gradient.
+ * loss_out / rmsd_out fp32 [n_repeat, n_ligands], terms_out fp32 [n_repeat, n_ligands, 2] = (interaction, configuration): the loss of
+ * the LAST epoch before its step, the RMSD after the last step.  trace_loss / trace_rmsd (both or neither, may be NULL): fp32
+ * [n_repeat, n_ligands, epochs], every epoch's loss and RMSD.
+ * max_atoms <= 512, max_pocket <= 4096 (largest ligand / pocket of the batch); max_con = most list entries of one ligand, max_y =
+ * largest residues_l * (atoms_l | 1): both only decide whether the lists and y_pred are kept in LDS (144 KiB budget) or read from memory.
+ * rate_lr: HOST pointer to two doubles, {config_rate, lr} (read before the call returns): the schedule weight and Adam's bias-corrected
+ * step are formed in double from them, as torch forms them from python floats.  Modes 0 / 1 iterate in float, mode 2 in double.
+ * Fixed-order sums, no atomics: a ligand's result does not depend on the batch or on n_repeat, and is bit-reproducible.
+ * Backward-compatible addition under ABI 19. */
+int fabind_distmap_generate(const float* x0, const float* truth, const float* pocket, const int* pocket_off, const float* y_pred,
+                            const long long* y_off, const int* atom_off, const int* con_ptr, const int* con_idx, const float* con_d,
+                            int n_ligands, int n_repeat, int n_atoms, int max_atoms, int max_pocket, int max_con, long max_y,
+                            int excluded_volume, int mode, int epochs, int config_start, const double* rate_lr, float* x_out,
+                            float* loss_out, float* terms_out, float* rmsd_out, float* trace_loss, float* trace_rmsd,
+                            hipStream_t stream);
+
 /* Ligand automorphisms (FABind_plus/fabind/utils/isomorphism.py:23-72: graph-tool subgraph_isomorphism(G, G, vertex_label=atomGetnum,
  * subgraph=False), run per molecule offline by tools/inject_isomorphism_to_data.py) for a BATCH of ligands, one wave per ligand.
  * labels: int32 [sum atoms]; nbr_ptr int32 [sum atoms + 1] / nbr_idx int32 (GLOBAL atom ids): symmetrised bond lists (every bond

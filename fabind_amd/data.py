@@ -9,8 +9,10 @@ pocket crop around the ligand centroid (+ the < 5 residues fallback), initial po
 centre), the `[glb_c | ligand | glb_p | protein]` node layouts of both graphs with their segment / mask / is_global /
 batch vectors, offset edge lists, the clamped pocket-ligand distance map, pocket labels -- is computed for all complexes
 at once with batched index arithmetic on the GPU.  Production configuration of the reference only:
-`compound_coords_init_mode='pocket_center_rdkit'`, `use_compound_com_as_pocket=True`, `use_whole_protein=False`,
-no torsion noise / local_eval (those branches need RDKit)."""
+`compound_coords_init_mode='pocket_center_rdkit'`, `use_compound_com_as_pocket=True`, `use_whole_protein=False`, no local_eval
+(that branch needs RDKit).  The train-time augmentation of the start conformer -- `random_rotation` (data.py:80-85 ->
+utils/utils.py:307-311) and FABind+'s torsion noise (utils/utils.py:285-304) -- is optional and runs in csrc/conformer.hip
+(fabind_amd/conformer.py); both are off by default."""
 import numpy as np
 import torch
 
@@ -57,7 +59,9 @@ def _pinned(n, dtype, depth=3):
 def pack_samples(samples, pin=True):
     """Host side: flatten a list of raw complexes into (float32 buffer, int64 buffer, layout).  Each sample is a mapping
     with `protein_node_xyz [L,3]`, `protein_esm2_feat [L,Fp]`, `coords [Nc,3]` (native ligand), `compound_node_features
-    [Nc,Fc]`, `rdkit_coords [Nc,3]`, `input_atom_edge_list [Eb,>=2]`, `LAS_edge_index [2,El]` (array-likes), `pdb`."""
+    [Nc,Fc]`, `rdkit_coords [Nc,3]`, `input_atom_edge_list [Eb,>=2]`, `LAS_edge_index [2,El]` (array-likes), `pdb`.
+    Optional, in all samples or in none: `bond_codes [Eb]` aligned with `input_atom_edge_list` (`symmetry.bond_code` coding; what
+    `build_batch(torsion_noise=True)` needs) and `augment_key` (an int naming the complex for the augmentation's random draws)."""
     a = lambda v, dt: np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=dt)
     floats, lay = [], {"n": len(samples)}
     for f in FLOAT_FIELDS:
@@ -68,7 +72,17 @@ def pack_samples(samples, pin=True):
     las = [a(s["LAS_edge_index"], np.int64).T for s in samples]
     counts = np.array([[s_["protein_node_xyz"].shape[0], s_["coords"].shape[0], b.shape[0], l.shape[0]]
                        for s_, b, l in zip(samples, bonds, las)], dtype=np.int64)
-    ints = np.concatenate([counts.reshape(-1)] + [b.reshape(-1) for b in bonds] + [l.reshape(-1) for l in las])
+    tail = []
+    if any("bond_codes" in s_ for s_ in samples):
+        if not all("bond_codes" in s_ for s_ in samples):
+            raise ValueError("fabind_amd.data: the field bond_codes must be given for every sample of a batch or for none")
+        tail = [a(s_["bond_codes"], np.int64).reshape(-1) for s_ in samples]
+        if any(c.shape[0] != b.shape[0] for c, b in zip(tail, bonds)):
+            raise ValueError("fabind_amd.data: bond_codes must hold one code per row of input_atom_edge_list")
+        lay["bond_codes"] = True
+    if samples and all("augment_key" in s_ for s_ in samples):
+        lay["augment_key"] = [int(s_["augment_key"]) for s_ in samples]
+    ints = np.concatenate([counts.reshape(-1)] + [b.reshape(-1) for b in bonds] + [l.reshape(-1) for l in las] + tail)
     n_f = sum(p.size for p in floats)
     if pin and torch.cuda.is_available():
         # rotating pool of page-locked staging buffers (allocating + locking ~0.5 GB per batch would cost more than the copy)
@@ -85,10 +99,16 @@ def pack_samples(samples, pin=True):
 
 @torch.no_grad()
 def build_batch(samples, device, pocket_radius=20.0, interaction_threshold=10.0, add_noise_to_com=None,
-                pocket_idx_no_noise=True, generator=None, packed=None):
+                pocket_idx_no_noise=True, generator=None, packed=None, random_rotation=False, torsion_noise=False, augment_seed=0,
+                augment_keys=None):
     """-> HeteroBatch on `device` with every field of SURVEY.md A.10 (what `IaBNet.forward / inference`, the losses and the
     evaluation loop read).  `add_noise_to_com`: uniform +-noise on the crop centre (the reference's train-time option,
-    utils/utils.py:129-130), drawn from `generator`."""
+    utils/utils.py:129-130), drawn from `generator`.
+    `random_rotation`: the start conformer `rdkit_coords` is replaced by its uniformly rotated image before the initial pose is
+    formed (the reference's train group, utils/utils.py:307-311).  `torsion_noise` (FABind+ --train-ligand-torsion-noise,
+    :285-304): the start conformer is made from the NATIVE ligand `coords` instead -- every rotatable bond set to a uniform random
+    dihedral, centred, rotated; needs the sample field `bond_codes`.  Draws are keyed by (`augment_seed`, key of the complex):
+    `augment_keys` [B], else the samples' `augment_key`, else the position in the batch.  Both off: the code path without them."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("fabind_amd.data.build_batch assembles batches on a HIP device; got %s" % dev)
@@ -138,6 +158,8 @@ def build_batch(samples, device, pocket_radius=20.0, interaction_threshold=10.0,
     pocket, pocket_b = prot[keep], pb[keep]
     Pk = torch.bincount(pocket_b, minlength=B)
     pocket_centre = _seg_mean(pocket, pocket_b, B)
+    if random_rotation or torsion_noise:
+        rdk = _augment(lig, rdk, bonds, idv, lay, Nc, bb, nb, nl, torsion_noise, augment_seed, augment_keys)
     init = rdk - _seg_mean(rdk, cb, B)[cb] + pocket_centre[cb]          # 'pocket_center_rdkit' (utils/utils.py:315-321)
     init_w = init - _seg_mean(init, cb, B)[cb]
 
@@ -184,6 +206,26 @@ def build_batch(samples, device, pocket_radius=20.0, interaction_threshold=10.0,
     data.pocket_residue_center = pocket_centre                 # FABind+ (model.py:176-183)
     data.pdb = lay["pdb"]
     return data
+
+
+def _augment(lig, rdk, bonds, idv, lay, Nc, bb, nb, nl, torsion_noise, seed, keys):
+    """The augmented start conformer of every ligand of the batch (fabind_amd/conformer.py), on the current stream."""
+    from . import conformer
+    B = lay["n"]
+    aoff = _offsets(Nc)
+    if keys is None:
+        keys = lay.get("augment_key")
+    if not torsion_noise:                                      # utils/utils.py:307-311: ((x - mean) @ M) + mean @ M
+        return conformer.perturb_conformers(rdk, None, 1, seed, keys, torsion_noise=False, random_rotation=True, centre=False,
+                                            atom_off=aoff)[0]
+    if not lay.get("bond_codes"):
+        raise ValueError("fabind_amd.data.build_batch(torsion_noise=True) needs the sample field bond_codes "
+                         "(one code per row of input_atom_edge_list)")
+    codes = idv[4 * B + 2 * nb + 2 * nl:4 * B + 2 * nb + 2 * nl + nb]
+    plan = conformer.rotatable_bonds((bonds + aoff[bb][:, None]).t(), codes, aoff, on_overflow="truncate")
+    # :285-304: torsions set on the crystal ligand, CanonicalizeConformer (centroid to the origin), uniform_random_rotation; a
+    # second rotation under random_rotation composes to one uniform rotation
+    return conformer.perturb_conformers(lig, plan, 1, seed, keys, torsion_noise=True, random_rotation=True, centre=True)[0]
 
 
 class DeviceFeeder:

@@ -77,6 +77,7 @@ const char* fabind_last_error(void);
  *     Likewise fabind_pose_stats / fabind_rank_loss_fwd (csrc/ranking.hip: FABind+ confidence training).
  *     Likewise the form report of csrc/norm.hip (fabind_layernorm_rows_form, _rows_bwd_form, fabind_row_stats_form, fabind_edge_lnfold_form /
  *     _blocks, fabind_edge_lnfold_bwd_form, fabind_inter_coord_fold_blocks + FB_LNR_* / FB_LNB_* / FB_RST_* / FB_ELF_* / FB_ELB_*).
+ *     Likewise fabind_torsion_plan / fabind_conformer_perturb (csrc/conformer.hip: train-time torsion noise and random rotation).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -491,6 +492,33 @@ int fabind_sym_automorphisms(const int* labels, const int* nbr_ptr, const int* n
 int fabind_sym_score(const float* pred, int n_pose, int n_atoms, const float* ref, const int* atom_off, const int* flat_off,
                      const int* auto_cnt, const int* flat, int n_ligands, int max_atoms, float* min_rmsd, int* arg_rmsd, float* min_sl1,
                      int* arg_sl1, int* best_idx, hipStream_t stream);
+/* Train-time ligand augmentation (FABind_plus/fabind/utils/utils.py:155-190 get_torsions, :285-304 torsion noise, :45-81 / :307-311
+ * uniform_random_rotation) for a BATCH of ligands.
+ * fabind_torsion_plan: the rotatable bonds of every ligand and the atoms each one moves.  nbr_ptr int32 [sum atoms + 1] / nbr_idx
+ *   (GLOBAL atom ids) / nbr_code / nbr_own int32 [n_entries]: the symmetrised, de-duplicated neighbour lists, sorted by owner and then
+ *   by neighbour, with the bond code of every entry (AROMATIC 1, TRIPLE 2, DOUBLE 3, SINGLE 4, other 5) and its owner atom;
+ *   atom_off int32 [n_ligands + 1].  j-k (j < k) is rotatable iff its code is SINGLE, j and k have heavy-atom degree >= 2, neither has
+ *   a TRIPLE bond and the bond is on no cycle (the SMARTS [!$(*#*)&!D1]-&!@[!$(*#*)&!D1] on the heavy-atom graph).
+ *   Count mode (quad = NULL): flag int32 [n_entries], scratch_quad int32 [4 n_entries], scratch_side uint32 [8 n_entries] are written
+ *   per entry; count[b] = rotatable bonds of ligand b; status[b] = 0, or 3 for a ligand of more than 256 atoms (zero torsions).
+ *   Write mode (the same flag / scratch buffers, tor_off int32 [n_ligands + 1] = exclusive sums of count): ligand b's torsions in
+ *   ascending (j, k) order at [tor_off[b], tor_off[b + 1]): quad[t] = (i, j, k, l) local atom ids, i / l the lowest-index neighbour of
+ *   j other than k / of k other than j; side[t] = eight 32-bit words, bit a of the 256-bit set <=> atom a is in k's component once
+ *   j-k is removed.  Integer arithmetic only.
+ * fabind_conformer_perturb: out fp32 [n_copies, n_atoms, 3] = n_copies perturbed images of x fp32 [n_atoms, 3]; one wave per (ligand,
+ *   copy).  The torsions of the plan (tor_off / quad / side; tor_off = NULL: none) are set one after another to their targets (rotation
+ *   of `side` about j -> k by target - current dihedral; by target itself when `relative`; a degenerate dihedral counts as 0), then,
+ *   with `rotate`, the rotation M = -(H R) of uniform_random_rotation: out = (x - mean) M + mean M, without the last term (centroid at
+ *   the origin) when `centre`.  Targets: angles fp32 [n_copies, t_total] (radians) or, angles = NULL, 2 pi u; (x1, x2, x3):
+ *   uniforms fp32 [n_copies, n_ligands, 3] or, NULL, drawn; u(seed, key, copy, draw) is a counter-based hash of its four arguments
+ *   (keys int32 [n_ligands]; NULL = the ligand's position), draws 0 .. T_b - 1 the torsions, then x2, x3, x1.  Fixed summation order:
+ *   bit-reproducible.  Ligands of more than 256 atoms are rotated only. */
+int fabind_torsion_plan(const int* nbr_ptr, const int* nbr_idx, const int* nbr_code, const int* nbr_own, const int* atom_off,
+                        int n_ligands, int n_entries, int* flag, int* scratch_quad, unsigned* scratch_side, int* count, int* status,
+                        const int* tor_off, int* quad, unsigned* side, hipStream_t stream);
+int fabind_conformer_perturb(const float* x, const int* atom_off, int n_ligands, int n_atoms, int n_copies, const int* tor_off,
+                             const int* quad, const unsigned* side, const float* angles, int t_total, const float* uniforms,
+                             const int* keys, unsigned seed, int relative, int rotate, int centre, float* out, hipStream_t stream);
 /* FABind+ confidence training (FABind_plus/fabind/utils/training_confidence.py:41-77, :215-252).
  * fabind_pose_stats: per sample b over the atoms [atom_off[b], atom_off[b + 1]) (atom_off int32 [B + 1]; pred / truth fp32 [n_atoms, 3]):
  *   rmsd[b] = sqrt(mean_i |p_i - t_i|^2), cdis[b] = |mean_i (p_i - t_i)| (the distance of the two centroids); an empty sample gives

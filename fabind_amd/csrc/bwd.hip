@@ -413,6 +413,8 @@ __global__ __launch_bounds__(256) void gather_dact_kernel(const float* dout, int
 extern "C" int fabind_gather_dact(const float* dout, int ldo, const int* row, const void* Z, int z_dt, int act, void* dZ,
                                   int dz_dt, int E, int H, hipStream_t stream) {
     if (E <= 0) return 0;
+    FB_REQUIRE(H % 4 == 0 && ldo % 4 == 0, "fabind_gather_dact: H and ldo must be multiples of 4");
+    FB_REQUIRE((uintptr_t)dout % 16 == 0, "fabind_gather_dact: 16-byte alignment");
     hipLaunchKernelGGL(gather_dact_kernel, dim3((E + 3) / 4), dim3(256), 0, stream, dout, ldo, row, Z, z_dt, act, dZ,
                        dz_dt, E, H);
     FB_CHECK_LAUNCH();

@@ -1864,7 +1864,8 @@ __global__ __launch_bounds__(256) void colsum_part_kernel(const void* in, int in
     const int c = blockIdx.x * 256 + lane * 4;
     const int r0 = blockIdx.y * rows_per, r1 = min(R, r0 + rows_per);
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool vec = (c + 3 < C) && (ldi % 4 == 0);
+    // 4-wide loads need a 16-byte (fp32) / 8-byte (bf16) aligned base: a column-offset view (buf[:, 1:]) takes the scalar path
+    const bool vec = (c + 3 < C) && (ldi % 4 == 0) && ((uintptr_t)in % (in_dt == FB_DT_BF16 ? 8 : 16) == 0);
     if (vec) {
         int r = r0 + q;
         for (; r + 12 < r1; r += 16) {          // 4 independent loads in flight per lane

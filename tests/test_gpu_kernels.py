@@ -143,8 +143,9 @@ def test_segment_sum_and_scan():
         row = torch.repeat_interleave(torch.arange(3000), deg.long())
         ref = torch.zeros(3000, H).index_add_(0, row, torch.nn.functional.silu(Z))
         assert (out.cpu() - ref).abs().max() <= 1e-4 * max(1.0, ref.abs().max())
-    # bf16 rows take the edge-balanced path (64 positions per wave, cut rows finish with atomics); also the
-    # permuted reduction (eidx) used for the sending side, on a buffer that holds stale values before the call
+    # bf16 rows: one wave sums a row of up to heavy_min edges alone (segment_sum_kernel), the 1700-edge row is left to the 16 waves of
+    # the cooperative kernel (segment_sum_heavy_kernel, fixed-order combine through LDS, no atomics); also the permuted reduction (eidx)
+    # used for the sending side, on a buffer that holds stale values before the call.  tests/test_gpu_reduce_forms.py walks the classes.
     deg[:7] = 0
     deg[2990:] = 0
     rp = K.exclusive_scan(deg.to(dev))

@@ -310,6 +310,10 @@ __global__ __launch_bounds__(256) void block_hadamard_bwd_kernel(const PairBlock
     // (NL == 1, W = 512: every thread of the work-group walks the SAME protein -- row bases are wave-uniform: scalar registers + one lane offset)
     const int ct = (NL == 1) ? (int)threadIdx.x : (int)threadIdx.x % CT, il = (NL == 1) ? 0 : (int)threadIdx.x / CT, c2 = ct * 2;
     extern __shared__ float sm[];                          // [NL][PB_CH][W] for the lane reduction (NL > 1 only)
+    if (d.C == 0) {                                        // a complex without atoms: no chunk runs, its rows of d tp are zeros (the caller hands over empty_like)
+        for (int i = i0 + il; i < i1; i += NL) *(float2*)(dtp + (size_t)(d.p_row0 + i) * lddp + c2) = make_float2(0.f, 0.f);
+        return;
+    }
     for (int j0 = 0, ch = 0; j0 < d.C; j0 += PB_CH, ++ch) {
         const int cw = min(PB_CH, d.C - j0);
         // this thread's two columns of the chunk's tc rows and of its d tc accumulators: registers (rows past the chunk: zeros)
@@ -416,8 +420,8 @@ extern "C" int fabind_pair_dist_fwd(const void* desc, int B, int n_tiles, const 
 }
 extern "C" int fabind_pair_dist_bwd(const void* desc, int B, int max_C, const float* xp, const float* xc, const float* dy, float scale,
                                     float lo, float hi, float* part, float* dxc, hipStream_t stream) {
-    if (B <= 0) return 0;
-    FB_REQUIRE(part && dxc && max_C > 0, "fabind_pair_dist_bwd: scratch [B][8][max_C][3] and the output are required");
+    if (B <= 0 || max_C <= 0) return 0;                    // (no complex has atoms: d xc has no rows)
+    FB_REQUIRE(part && dxc, "fabind_pair_dist_bwd: scratch [B][8][max_C][3] and the output are required");
     hipLaunchKernelGGL(pair_dist_bwd_kernel, dim3(B, 8), dim3(256), 0, stream, (const PairBlock*)desc, xp, xc, dy, scale, lo, hi, max_C, part);
     FB_CHECK_LAUNCH();
     hipLaunchKernelGGL(pair_dist_bwd_reduce_kernel, dim3(B), dim3(256), 0, stream, (const PairBlock*)desc, B, max_C, part, dxc);
@@ -445,7 +449,7 @@ extern "C" int fabind_block_hadamard_bwd(const void* desc, int B, int n_tiles, c
     FB_REQUIRE(W == 64 || W == 128 || W == 256 || W == 512, "fabind_block_hadamard_bwd: W in {64, 128, 256, 512}");
     FB_REQUIRE(ldo % 2 == 0 && ldtp % 2 == 0 && lddp % 2 == 0 && ((((uintptr_t)dout) & 3) == 0) && ((((uintptr_t)tp | (uintptr_t)dtp | (uintptr_t)part) & 7) == 0),
                "fabind_block_hadamard_bwd: alignment (bf16 pairs / float2)");
-    if (B <= 0 || n_tiles <= 0) return 0;
+    if (B <= 0) return 0;
 #define BH_LAUNCH(WW)                                                                                                              \
     do {                                                                                                                           \
         constexpr int NL_ = 256 / (WW / 2);                                                                                        \
@@ -455,9 +459,11 @@ extern "C" int fabind_block_hadamard_bwd(const void* desc, int B, int n_tiles, c
         hipLaunchKernelGGL((block_hadamard_bwd_kernel<WW>), dim3(n_tiles), dim3(256), lds, stream, (const PairBlock*)desc, B,      \
                            (const bf16_t*)dout, ldo, tp, ldtp, tc, ldtc, dtp, lddp, nchunk_max, part);                             \
     } while (0)
-    if (W == 512) BH_LAUNCH(512); else if (W == 256) BH_LAUNCH(256); else if (W == 128) BH_LAUNCH(128); else BH_LAUNCH(64);
+    if (n_tiles > 0) {                                     // (no complex has residues: no tile, and the reduction below writes the zeros of d tc)
+        if (W == 512) BH_LAUNCH(512); else if (W == 256) BH_LAUNCH(256); else if (W == 128) BH_LAUNCH(128); else BH_LAUNCH(64);
+        FB_CHECK_LAUNCH();
+    }
 #undef BH_LAUNCH
-    FB_CHECK_LAUNCH();
     if (n_crows > 0) {
         hipLaunchKernelGGL(block_hadamard_bwd_reduce_kernel, dim3(n_crows), dim3(256), 0, stream, (const PairBlock*)desc, B, row_b, W,
                            nchunk_max, part, dtc, lddc);

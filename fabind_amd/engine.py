@@ -138,10 +138,7 @@ class Layout:
     def ranges(self, idx_first):
         """Per-complex [start,end) offsets of a complex-contiguous edge list given its first-node ids."""
         if idx_first.is_cuda and idx_first.dtype == torch.int32 and idx_first.is_contiguous():
-            out = torch.empty(self.B + 1, dtype=torch.int32, device=idx_first.device)       # one kernel: a binary search per complex
-            K.check(K._lib.load().fabind_lower_bound(K.ptr(idx_first), idx_first.shape[0], K.ptr(self.node_off), self.B + 1, K.ptr(out),
-                                                     K.stream()), "fabind_lower_bound")
-            return out
+            return K.lower_bound(idx_first, self.node_off, self.B + 1)       # one kernel: a binary search per complex
         which = torch.bucketize(idx_first, self.node_off[1:].to(idx_first.dtype), right=True)
         cnt = _count(which, self.B)
         out = torch.zeros(self.B + 1, dtype=torch.int32, device=idx_first.device)

@@ -53,14 +53,17 @@ def _ld(t):
 def gemm(A, W, bias=None, A2=None, act_pro=ACT_NONE, act_epi=ACT_NONE, residual=None, r_index=None,
          out=None, out_dtype=torch.float32, want_out=True, dotvec=None, aux=None, dact=ACT_NONE, alpha=1.0,
          accumulate=False, groups=None, n_groups=0, max_m=0, max_n=0, M=None, N=None, ldc=None, k_splits=1,
-         out2=None, groups_ext=False, p_drop=0.0, seed=0, out16=None, flops=None, force_x3=False):
+         out2=None, groups_ext=False, p_drop=0.0, seed=0, out16=None, flops=None, force_x3=False, store_preact=False, fold=None,
+         nbytes=None):
     """C = epi(pro([A|A2]) @ W^T); see FabindGemmArgs.  Returns (C or None, dot_partials or None).  out16: bf16 tensor that
     receives a copy of an fp32 C (plain bias / residual epilogues only).
 
     `groups` (int32 [G,8] device tensor) selects the ragged-batched mode; then `out` must be given.
     flops: executed multiply-add flops of a ragged launch (bench.py's live roofline accounting; default 2 M N K, which for a
     grouped launch is the padded bounding box, not the work).
-    force_x3: fp32 A and fp32 W contracted as split bf16 whatever the precision mode (config.set_split_sites: single sites of the bf16 mode)."""
+    force_x3: fp32 A and fp32 W contracted as split bf16 whatever the precision mode (config.set_split_sites: single sites of the bf16 mode).
+    store_preact: C receives the value before act_epi (the row-dot still sees act_epi(v)).  fold = (row_mu, row_rs, col_c): LayerNorm of
+    the rows of A folded into the epilogue.  nbytes: the HBM bytes bench.py prices the launch at (default: the algorithmic figure below)."""
     lib = _lib.load()
     a = GemmArgs()
     K1 = A.shape[1]
@@ -96,7 +99,9 @@ def gemm(A, W, bias=None, A2=None, act_pro=ACT_NONE, act_epi=ACT_NONE, residual=
     if A2 is not None:
         assert A2.dtype == A.dtype
     a.act_pro, a.act_epi, a.dact_epi = act_pro, act_epi, dact
-    a.accumulate = 1 if accumulate else 0
+    a.accumulate, a.store_preact = 1 if accumulate else 0, 1 if store_preact else 0
+    if fold is not None:
+        a.row_mu, a.row_rs, a.col_c = ptr(fold[0]), ptr(fold[1]), ptr(fold[2])
     a.n_groups, a.max_m, a.max_n = n_groups, max_m, max_n
     a.k_splits = k_splits
     a.groups_ext = 1 if groups_ext else 0
@@ -115,8 +120,8 @@ def gemm(A, W, bias=None, A2=None, act_pro=ACT_NONE, act_epi=ACT_NONE, residual=
     if groups is not None:
         label += " (ragged, %d groups)" % n_groups
     # algorithmic HBM bytes: every operand read once, every result written once (ragged launches: not counted)
-    nb = 0.0
-    if groups is None:
+    nb = 0.0 if nbytes is None else nbytes
+    if groups is None and nbytes is None:
         mn = float(M) * N
         nb = float(M) * K * A.element_size() + float(N) * K * W.element_size()
         nb += mn * out.element_size() * (2 if accumulate else 1) if want_out else 0.0
@@ -130,9 +135,19 @@ def gemm(A, W, bias=None, A2=None, act_pro=ACT_NONE, act_epi=ACT_NONE, residual=
     return (out if want_out else None), dot_out
 
 
+def _nchunk(rows):
+    """Row chunks of the column-partials scratch of colsum and rowdot_bwd."""
+    return max(1, min(1024, (rows + 255) // 256))
+
+
+def _nchunk_fused(rows):
+    """Row chunks of mul_dact_colsum / mul_dropmask_colsum: >= 2 blocks per SIMD at C = 512 (the pass is latency-bound)."""
+    return max(1, min(4096, (rows + 63) // 64))
+
+
 def colsum(x, out=None, accumulate=False):
     R, C = x.shape
-    nchunk = max(1, min(1024, (R + 255) // 256))
+    nchunk = _nchunk(R)
     scratch = torch.empty((nchunk, C), dtype=torch.float32, device=x.device)
     if out is None:
         out = torch.empty((C,), dtype=torch.float32, device=x.device)
@@ -278,15 +293,19 @@ CROSS_ATTN_FUSED_MAX_C = 62
 def bo_tiles(lay):
     """(toff [B+1], tile_b [n_tiles], n_tiles) of the packed ligand-side operand of the fused cross attention: complex b owns
     ceil(C_b / 2) 16-column tiles (cached on the layout)."""
-    c = getattr(lay, "_bo_tiles", None)
+    return _ligand_steps(lay, "_bo_tiles", 2)
+
+
+def _ligand_steps(lay, attr, per):
+    """(offsets [B+1], owner complex of every step, steps) when complex b owns ceil(C_b / per) steps (cached on the layout as `attr`)."""
+    c = getattr(lay, attr, None)
     if c is None:
-        import numpy as np
-        T = (np.asarray(lay.C) + 1) // 2
-        toff = np.concatenate([[0], np.cumsum(T)]).astype(np.int32)
-        tile_b = np.repeat(np.arange(lay.B, dtype=np.int32), T)
-        dev = lay.node_off.device
         from .param_pack import upload
-        c = lay._bo_tiles = (upload(toff, dev, torch.int32), upload(tile_b, dev, torch.int32), int(toff[-1]))
+        T = (np.asarray(lay.C) + per - 1) // per
+        off = np.concatenate([[0], np.cumsum(T)]).astype(np.int32)
+        dev = lay.node_off.device
+        c = (upload(off, dev, torch.int32), upload(np.repeat(np.arange(lay.B, dtype=np.int32), T), dev, torch.int32), int(off[-1]))
+        setattr(lay, attr, c)
     return c
 
 
@@ -324,15 +343,7 @@ def cross_attn_fused_fwd(q, k, v, gpre, a0_16, bo, bconst8, lay, H, mode, scale,
 def bot_ksteps(lay):
     """(koff [B+1], kstep_b [n_ksteps], n_ksteps) of the packed operand of the fused attention backward's d a0 contraction: complex b
     owns ceil(C_b / 4) k-steps of 4 ligand-side nodes (cached on the layout)."""
-    c = getattr(lay, "_bot_ksteps", None)
-    if c is None:
-        KS = (np.asarray(lay.C) + 3) // 4
-        koff = np.concatenate([[0], np.cumsum(KS)]).astype(np.int32)
-        kstep_b = np.repeat(np.arange(lay.B, dtype=np.int32), KS)
-        dev = lay.node_off.device
-        from .param_pack import upload
-        c = lay._bot_ksteps = (upload(koff, dev, torch.int32), upload(kstep_b, dev, torch.int32), int(koff[-1]))
-    return c
+    return _ligand_steps(lay, "_bot_ksteps", 4)
 
 
 def cross_attn_fused_bwd(qg, kv, a0_16, bo, bconst8, lay, H, mode, scale, out, lse, dout, dqg, dkv, acat, kcol0, colpart, kp):
@@ -378,7 +389,10 @@ def pair_bmat(b0, wcomp, c_node, out_dtype):
 
 
 def pair_hadamard(a0, b0, a1, b1, red_p, red_c, out_dtype):
-    H, H2 = a0.shape[1], a1.shape[1]
+    """a1 / b1 None: no second operand pair (the first pair's pointers again, width 0)."""
+    H, H2 = a0.shape[1], 0 if a1 is None else a1.shape[1]
+    if a1 is None:
+        a1, b1 = a0, b0
     n_red = red_p.shape[0]
     hd = torch.empty((n_red, H + H2), dtype=out_dtype, device=a0.device)
     assert a0.stride(0) == b0.stride(0) and a1.stride(0) == b1.stride(0)
@@ -537,15 +551,8 @@ def node_chain_x3_pack_many(chains):
 def node_chain_x3_pack(W1, W2, kind):
     """hi | lo fragment packs of the H x H blocks of a chain's two fp32 master weights (node_chain_x3_fwd): 8 packs in the order
     (W1a hi, lo, W1b hi, lo, W2a hi, lo, W2b hi, lo); kind as in node_chain_pack."""
-    H = W2.shape[0]
-    if kind == 0:
-        assert W1.shape == (H, 2 * H) and W2.shape == (H, H)
-        blocks = (W1[:, :H], W1[:, H:], W2, None)
-    else:
-        assert W1.shape == (2 * H, H) and W2.shape == (H, 2 * H)
-        blocks = (W1[:H], W1[H:], W2[:, :H], W2[:, H:])
     out = []
-    for b_ in blocks:
+    for b_ in node_chain_x3_blocks(W1, W2, kind):
         out.extend(pack_frag_split(b_.contiguous()) if b_ is not None else (None, None))
     return tuple(out)
 
@@ -1127,3 +1134,418 @@ def gemm_tn(Y, X, splits=None, out_dtype=torch.float32, with_colsum=False):
     if with_colsum:
         return out[:M * N].view(M, N), out[M * N:].float()
     return out.view(M, N)
+
+
+# ------------------------------------------------------------------------------------------------
+# the adjoint kernels and the heads: what the autograd nodes of ops.py, engine.py and plus/engine.py launch
+# ------------------------------------------------------------------------------------------------
+def transpose_act(x, Rp, out_dtype, act=ACT_NONE):
+    """act(x)^T as an out_dtype [C, Rp] matrix, the columns beyond R zero (operands of K = R contractions)."""
+    R, C = x.shape
+    out = torch.empty((C, Rp), dtype=out_dtype, device=x.device)
+    if Rp != R:
+        out[:, R:].zero_()
+    check(_lib.load().fabind_transpose_act(ptr(x), dt_code(x.dtype), _ld(x), ptr(out), dt_code(out_dtype), Rp, R, C, act, stream()),
+          "fabind_transpose_act")
+    return out
+
+
+def mul_dact(dy, aux, act, out_dtype, scale=1.0):
+    """scale * dy * act'(aux) as out_dtype (aux None: a cast of dy)."""
+    out = torch.empty(dy.shape, dtype=out_dtype, device=dy.device)
+    a = aux if aux is not None else dy
+    check(_lib.load().fabind_mul_dact(ptr(dy), dt_code(dy.dtype), ptr(a), dt_code(a.dtype), act, ptr(out), dt_code(out_dtype),
+                                      dy.numel(), float(scale), stream()), "fabind_mul_dact")
+    return out
+
+
+def mul_dact_colsum(dy, aux, act, out_dtype, scale=1.0):
+    """(scale * dy * act'(aux), its column sums) in one pass (bias gradient fused into the activation adjoint / cast)."""
+    R, C = dy.shape
+    out = torch.empty((R, C), dtype=out_dtype, device=dy.device)
+    nchunk = _nchunk_fused(R)
+    scratch = torch.empty((nchunk, C), dtype=torch.float32, device=dy.device)
+    db = torch.empty(C, dtype=torch.float32, device=dy.device)
+    check(_lib.load().fabind_mul_dact_colsum(ptr(dy), dt_code(dy.dtype), ptr(aux), dt_code(aux.dtype) if aux is not None else 0,
+                                             act, ptr(out), dt_code(out_dtype), R, C, ptr(db), ptr(scratch), nchunk, float(scale),
+                                             stream()), "fabind_mul_dact_colsum")
+    return out, db
+
+
+def mul_dropmask_colsum(dy, p_drop, seed, out_dtype):
+    """(dy * keep(seed, r, c) / (1 - p), its column sums): the adjoint of a GEMM epilogue's dropout with the mask regenerated from its key."""
+    R, C = dy.shape
+    out = torch.empty((R, C), dtype=out_dtype, device=dy.device)
+    nchunk = _nchunk_fused(R)
+    scratch = torch.empty((nchunk, C), dtype=torch.float32, device=dy.device)
+    db = torch.empty(C, dtype=torch.float32, device=dy.device)
+    check(_lib.load().fabind_mul_dropmask_colsum(ptr(dy), dt_code(dy.dtype), ptr(out), dt_code(out_dtype), R, C, float(p_drop),
+                                                 int(seed) & 0xFFFFFFFF, ptr(db), ptr(scratch), nchunk, stream()),
+          "fabind_mul_dropmask_colsum")
+    return out, db
+
+
+def rowdot_bwd(z, dpart, u, act_epi):
+    """Adjoint of part = row-dot(act_epi(z), u) over the stored z -> (dz = dpart u act_epi'(z) as z.dtype, du fp32); dpart [M, tiles] contiguous."""
+    M, N = z.shape
+    dz = torch.empty_like(z)
+    nchunk = _nchunk(M)
+    scratch = torch.empty((nchunk, N), dtype=torch.float32, device=z.device)
+    du = torch.empty(N, dtype=torch.float32, device=z.device)
+    check(_lib.load().fabind_rowdot_bwd(ptr(z), dt_code(z.dtype), ptr(dpart), dpart.shape[1], ptr(u), act_epi, M, N,
+                                        ptr(dz), ptr(du), ptr(scratch), nchunk, stream()), "fabind_rowdot_bwd")
+    return dz, du
+
+
+def edge_geom_bwd(d, rho, norm, dd, drhohat, row, rowptr, colptr, perm, node_off, B, n):
+    """Adjoint of edge_geom -> dx [n, 3]; (colptr, perm): the edges grouped by their sending node."""
+    E, dev = row.shape[0], d.device
+    dx = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    gbuf, gnorm = torch.empty((max(E, 1), 3), dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev)
+    check(_lib.load().fabind_edge_geom_bwd(ptr(d), ptr(rho), ptr(norm), ptr(dd), ptr(drhohat), ptr(row), ptr(rowptr), ptr(colptr),
+                                           ptr(perm), ptr(node_off), B, E, n, ptr(dx), ptr(gbuf), ptr(gnorm), stream()),
+          "fabind_edge_geom_bwd")
+    return dx
+
+
+def gcl_pre_bwd(dpre, H, rhohat, w_r):
+    """The radial part of gcl_pre's adjoint -> (d rhohat [E], d w_r [H])."""
+    E = dpre.shape[0]
+    drh = torch.empty(E, dtype=torch.float32, device=dpre.device)
+    nchunk = max(1, min(2048, (E + 255) // 256))
+    scratch = torch.empty((nchunk, H), dtype=torch.float32, device=dpre.device)
+    dw = torch.empty(H, dtype=torch.float32, device=dpre.device)
+    check(_lib.load().fabind_gcl_pre_bwd(ptr(dpre), dt_code(dpre.dtype), H, ptr(rhohat), ptr(w_r), E, ptr(drh), ptr(dw),
+                                         ptr(scratch), nchunk, stream()), "fabind_gcl_pre_bwd")
+    return drh, dw
+
+
+def gather_dact(dout, row, Z, act):
+    """Adjoint of segment_sum(act(Z)): dZ[e] = dout[row[e]] * act'(Z[e])."""
+    dZ = torch.empty_like(Z)
+    check(_lib.load().fabind_gather_dact(ptr(dout), _ld(dout), ptr(row), ptr(Z), dt_code(Z.dtype), act, ptr(dZ),
+                                         dt_code(dZ.dtype), Z.shape[0], Z.shape[1], stream()), "fabind_gather_dact")
+    return dZ
+
+
+def coord_update_bwd(d, s, rowptr, dxo, mean, clampv):
+    """Adjoint of coord_update to the edge vectors and the per-edge scalars -> (dd [E, 3], ds [E])."""
+    E = s.shape[0]
+    dd = torch.empty((E, 3), dtype=torch.float32, device=d.device)
+    ds = torch.empty(E, dtype=torch.float32, device=d.device)
+    check(_lib.load().fabind_coord_update_bwd(ptr(d), ptr(s), ptr(rowptr), dxo.shape[0], 1 if mean else 0, clampv,
+                                              ptr(dxo), ptr(dd), ptr(ds), stream()), "fabind_coord_update_bwd")
+    return dd, ds
+
+
+def drop_mix(h, hn, p_drop, seed):
+    """h + dropout(hn - h) with the mask keyed by (seed, element) (csrc/bwd.hip: drop_mix_kernel)."""
+    out = torch.empty_like(h)
+    check(_lib.load().fabind_drop_mix(ptr(h), ptr(hn), ptr(out), h.numel(), float(p_drop), int(seed) & 0xFFFFFFFF, stream()),
+          "fabind_drop_mix")
+    return out
+
+
+def drop_mix_bwd(g, p_drop, seed):
+    """Adjoint of drop_mix with the mask regenerated -> (d hn, d h)."""
+    dhn, dh = torch.empty_like(g), torch.empty_like(g)
+    check(_lib.load().fabind_drop_mix_bwd(ptr(g), ptr(dhn), ptr(dh), g.numel(), float(p_drop), int(seed) & 0xFFFFFFFF, stream()),
+          "fabind_drop_mix_bwd")
+    return dhn, dh
+
+
+def cross_attn_bwd(qg, kv, bias, lin_col, gate_col, desc, B, max_nq, max_nk, scale, out, lse, dout, dqg, dkv, dbias, mfma):
+    """Adjoint of cross_attn_fwd into the caller's dqg / dkv / dbias; mfma: recompute the probabilities the way the forward did."""
+    lib = _lib.load()
+    dO = torch.empty((qg.shape[0], 128), dtype=torch.float32, device=qg.device)
+    Dv = torch.empty((qg.shape[0], 4), dtype=torch.float32, device=qg.device)
+    n_scr = int(lib.fabind_cross_attn_bwd_scratch(B, max_nq, max_nk))     # per-split partials of the short side (or 0)
+    scr = torch.empty(n_scr, dtype=torch.float32, device=qg.device) if n_scr else None
+    fn = lib.fabind_cross_attn_mfma_bwd if mfma else lib.fabind_cross_attn_bwd
+    check(fn(ptr(qg), _ld(qg), ptr(kv), _ld(kv), ptr(bias), _ld(bias), lin_col, gate_col, ptr(desc), B, max_nq,
+             max_nk, scale, ptr(out), ptr(lse), ptr(dout), ptr(dqg), ptr(dkv), ptr(dbias), ptr(dO), ptr(Dv), ptr(scr), stream()),
+          "fabind_cross_attn_bwd")
+
+
+def pair_hadamard_bwd(dhd, a0, b0, H, a1, b1, H2, red_p, red_c, da0, db0, da1, db1):
+    """Adjoint of pair_hadamard, added into da0 / db0 (and da1 / db1) with float atomics; a1 / b1 / da1 / db1 may be None (H2 = 0)."""
+    check(_lib.load().fabind_pair_hadamard_bwd(ptr(dhd), dt_code(dhd.dtype), _ld(dhd), ptr(a0), ptr(b0), _ld(a0), H, ptr(a1), ptr(b1),
+                                               _ld(a1) if a1 is not None else 0, H2, ptr(red_p), ptr(red_c), red_p.shape[0], ptr(da0),
+                                               ptr(db0), _ld(da0), ptr(da1), ptr(db1), _ld(da1) if da1 is not None else 0, stream()),
+          "fabind_pair_hadamard_bwd")
+
+
+def pair_hadamard_bwd_rows(dhd, T0, H, T1, H2, rowptr, col, red_idx, red_c, d0, d1):
+    """Adjoint of pair_hadamard over the inter graph's own rows: one wave per node, one writer per element (no float atomics)."""
+    check(_lib.load().fabind_pair_hadamard_bwd_rows(ptr(dhd), dt_code(dhd.dtype), _ld(dhd), ptr(T0), _ld(T0), H, ptr(T1), _ld(T1), H2,
+                                                    ptr(rowptr), ptr(col), ptr(red_idx), ptr(red_c), T0.shape[0], ptr(d0), _ld(d0),
+                                                    ptr(d1), _ld(d1), stream()), "fabind_pair_hadamard_bwd_rows")
+
+
+def pair_hadamard_bwd_grid(dhd, T, Hh, node_off, c_cnt, node_b, desc_p, N, dT):
+    """Adjoint of pair_hadamard over a batch's full protein x ligand grid: a deterministic row walk (csrc/bwd.hip)."""
+    check(_lib.load().fabind_pair_hadamard_bwd_grid(ptr(dhd), dt_code(dhd.dtype), _ld(dhd), ptr(T), _ld(T), Hh, ptr(node_off), ptr(c_cnt),
+                                                    ptr(node_b), ptr(desc_p), N, ptr(dT), _ld(dT), stream()),
+          "fabind_pair_hadamard_bwd_grid")
+
+
+def rows_hadamard_bwd(dout, t, rowptr, pair_idx, partner):
+    """Adjoint of out[e] = t[ia[e]] * t[ib[e]] as a row walk over the CSR of every row's pairs -> d t."""
+    dt_ = torch.empty_like(t)
+    check(_lib.load().fabind_rows_hadamard_bwd(ptr(dout), dt_code(dout.dtype), _ld(dout), ptr(t), _ld(t), t.shape[1], ptr(rowptr),
+                                               ptr(pair_idx), ptr(partner), t.shape[0], ptr(dt_), _ld(dt_), stream()),
+          "fabind_rows_hadamard_bwd")
+    return dt_
+
+
+def pair_block_tile_chunk():
+    """(pocket rows per tile, ligand rows per chunk) of the pair-block kernels (csrc/heads.hip)."""
+    return _lib.load().fabind_pair_block_tile(), _lib.load().fabind_pair_block_chunk()
+
+
+def block_hadamard_fwd(bl, t, n_a):
+    """out[pair] = t[pocket row] * t[n_a + ligand row] over the dense per-complex blocks `bl` (ops.PairBlocks) -> bf16 [pairs, W]."""
+    W = t.shape[1]
+    out = torch.empty((bl.n_pairs, W), dtype=torch.bfloat16, device=t.device)
+    check(_lib.load().fabind_block_hadamard_fwd(bl.desc_ptr, bl.B, bl.n_tiles, ptr(t), _ld(t), ptr(t[n_a:]), _ld(t), W, ptr(out), W,
+                                                stream()), "fabind_block_hadamard_fwd")
+    return out
+
+
+def block_hadamard_bwd(bl, dout, t, n_a):
+    """Adjoint of block_hadamard_fwd: one pass over dout, every row of d t written once -> d t."""
+    W = t.shape[1]
+    dt_ = torch.empty_like(t)
+    part = torch.empty((bl.n_tiles, bl.nchunk_max, bl.chunk, W), dtype=torch.float32, device=t.device)
+    check(_lib.load().fabind_block_hadamard_bwd(bl.desc_ptr, bl.B, bl.n_tiles, ptr(dout), _ld(dout), ptr(t), _ld(t), ptr(t[n_a:]), _ld(t),
+                                                W, bl.row_b_ptr, bl.n_crows, bl.nchunk_max, ptr(part), ptr(dt_), _ld(dt_),
+                                                ptr(dt_[n_a:]), _ld(dt_), stream()), "fabind_block_hadamard_bwd")
+    return dt_
+
+
+def inter_attn_bwd(qkv, cv, H, d, rhohat, rowptr, col, mirror, red_idx, w_rk, w_rv, wcr, w3, alpha, cvs, clampv, dh_out, dx_out, nblk,
+                   deal=None):
+    """Adjoint of inter_attn_fwd -> (dqkv, dcv, dd [E, 3], drh [E], dbias_red [E / 2], dcp [E], the column sums [4 H] of the four vector
+    gradients d w_rk | d w_rv | d wcr | d w3).  nblk: work-groups, one row of partials each; deal: see inter_attn_fwd."""
+    N, E = qkv.shape[0], col.shape[0]
+    f32 = dict(dtype=torch.float32, device=qkv.device)
+    dqkv = torch.empty_like(qkv)          # every row is written: d q by pass a (zeros for nodes without inter edges), d k | d v by pass b
+    dcv = torch.empty_like(cv)
+    # (pass a writes d d, d rhohat, d logit and d cp of EVERY edge -- each edge lies in one row's range: no pre-zeroing)
+    dd, drh = torch.empty((max(E, 1), 3), **f32), torch.empty(max(E, 1), **f32)
+    n_red = E // 2
+    dbias_red = torch.zeros(max(n_red, 1), **f32)
+    dlogit, dcp = torch.empty(max(E, 1), **f32), torch.empty(max(E, 1), **f32)
+    if E == 0:
+        dd.zero_(); drh.zero_()
+    wpart = torch.empty((nblk, 4 * H), **f32)                     # [block][4][H] partials of the four vector gradients
+    args = (ptr(qkv), _ld(qkv), ptr(cv), _ld(cv), H, ptr(d), ptr(rhohat), ptr(rowptr), ptr(col), ptr(mirror), ptr(red_idx), ptr(w_rk),
+            ptr(w_rv), ptr(wcr), ptr(w3), ptr(alpha), ptr(cvs), clampv, N, ptr(dh_out), ptr(dx_out), ptr(dqkv), ptr(dcv), ptr(dd), ptr(drh),
+            ptr(dbias_red), ptr(dlogit), ptr(dcp), ptr(wpart), nblk)
+    if deal is not None:             # the rows dealt by degree: heavy rows on four waves (csrc/inter_attn_rows.hip)
+        check(_lib.load().fabind_inter_attn_bwd_rows(*args, ptr(deal[0]), int(deal[1]), int(deal[2]), stream()), "fabind_inter_attn_bwd_rows")
+    else:
+        check(_lib.load().fabind_inter_attn_bwd(*args, stream()), "fabind_inter_attn_bwd")
+    return dqkv, dcv, dd[:E], drh[:E], dbias_red[:n_red], dcp[:E], colsum(wpart)       # (one launch pair for all four)
+
+
+def las_step_bwd(x, x0, mask, las_i, las_j, las_off, node_off, c_cnt, B, max_n, step, clampv, dout):
+    """Adjoint of las_step with the forward's own clamp decisions (mask) -> dx."""
+    dx = torch.empty_like(x)
+    check(_lib.load().fabind_las_step_bwd(ptr(x), ptr(x0), ptr(mask), ptr(las_i), ptr(las_j), ptr(las_off), ptr(node_off), ptr(c_cnt), B,
+                                          max_n, step, clampv, ptr(dout), ptr(dx), stream()), "fabind_las_step_bwd")
+    return dx
+
+
+def pair_bias_cat(douts, lay, H, Kp, b0, wcomp):
+    """The pair-bias gradients of all blocks (fp32 [pairs, 8] each, None for a block without one) as bf16 rows concatenated along K and
+    padded per complex, with the matching b0 * wcomp operand -> (Acat [sumP, nblk Kp], BTcat [B H, nblk Kp], per-work-group column
+    sums of the gradients [parts, nblk 8])."""
+    nblk, dev = len(douts), b0.device
+    Acat = torch.empty((lay.sumP, nblk * Kp), dtype=torch.bfloat16, device=dev)
+    BTcat = torch.empty((lay.B * H, nblk * Kp), dtype=torch.bfloat16, device=dev)
+    ptrs = (ctypes.c_void_p * nblk)(*[ptr(d) for d in douts])
+    colpart = torch.empty((int(_lib.load().fabind_pair_bias_cat_parts(lay.B, lay.max_P)), nblk * 8), dtype=torch.float32, device=dev)
+    check(_lib.load().fabind_pair_bias_cat(ptrs, nblk, ptr(lay.desc_p), lay.B, lay.max_P, Kp, ptr(Acat), _ld(Acat), ptr(b0), _ld(b0),
+                                   ptr(lay.c_index), ptr(wcomp), H, ptr(BTcat), _ld(BTcat), ptr(colpart), stream()), "fabind_pair_bias_cat")
+    return Acat, BTcat, colpart
+
+
+def pair_bias_btcat(b0, lay, wslot, H, Kp):
+    """The b0 * wslot operand of the d a0 contraction for all blocks (wslot fp32 [nblk, 8, H]) -> bf16 [B H, nblk Kp]."""
+    nblk = wslot.shape[0]
+    BTcat = torch.empty((lay.B * H, nblk * Kp), dtype=torch.bfloat16, device=b0.device)
+    check(_lib.load().fabind_pair_bias_btcat(ptr(b0), _ld(b0), ptr(lay.c_index), ptr(lay.desc_p), ptr(wslot), nblk, H, Kp, ptr(BTcat),
+                                             _ld(BTcat), lay.B, stream()), "fabind_pair_bias_btcat")
+    return BTcat
+
+
+def batched_transpose_pad(src, desc, B, nblk, Kp, Pp):
+    """Per complex and block the [rows, Kp] column slice of the bf16 rows `src` as a K-major, zero-padded [Kp, Pp] matrix -> [nblk, B Kp, Pp]."""
+    out = torch.empty((nblk, B * Kp, Pp), dtype=torch.bfloat16, device=src.device)
+    check(_lib.load().fabind_batched_transpose_pad(ptr(src), _ld(src), ptr(desc), B, nblk, Kp, Pp, ptr(out), stream()),
+          "fabind_batched_transpose_pad")
+    return out
+
+
+def pair_bias_finish_parts(sumC):
+    return int(_lib.load().fabind_pair_bias_finish_parts(sumC))
+
+
+def pair_bias_finish(T, a0b0, H, wrows, c_index, sumC, da0b0, fin):
+    """One block's ligand-side and weight gradients from T = D^T a0: d b0 added into da0b0, the d wcomp partials into the columns of `fin`
+    (a column slice of the [parts, nblk 8 H] buffer of all blocks)."""
+    check(_lib.load().fabind_pair_bias_finish(ptr(T), ptr(a0b0), _ld(a0b0), H, ptr(wrows), ptr(c_index), sumC, ptr(da0b0), ptr(fin),
+                                              _ld(fin), stream()), "fabind_pair_bias_finish")
+
+
+def pair_bias_bwd(dout, NO, a0b0, H, wrows, lay, da0b0):
+    """The fp32 adjoint of one block's pair bias (float atomics into da0b0) -> per-complex partials of d wcomp [B, NO H]."""
+    dwk = torch.zeros((lay.B, NO * H), dtype=torch.float32, device=a0b0.device)
+    check(_lib.load().fabind_pair_bias_bwd(ptr(dout), NO, ptr(a0b0), _ld(a0b0), H, ptr(wrows), ptr(lay.desc_p), lay.B, lay.max_P,
+                                           lay.max_C, ptr(lay.p_index), ptr(lay.c_index), ptr(da0b0), ptr(dwk), stream()),
+          "fabind_pair_bias_bwd")
+    return dwk
+
+
+def cross_attn_fused_bwd_parts(B, max_P):
+    return int(_lib.load().fabind_cross_attn_fused_bwd_parts(B, max_P))
+
+
+def layernorm_fwd(x, w, b, eps):
+    """LayerNorm of the rows of a contiguous fp32 x -> (y, mean [R], rstd [R])."""
+    R, C = x.shape
+    y = torch.empty_like(x)
+    mean = torch.empty(R, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(R, dtype=torch.float32, device=x.device)
+    check(_lib.load().fabind_layernorm_fwd(ptr(x), ptr(w), ptr(b), eps, R, C, ptr(y), ptr(mean), ptr(rstd), stream()),
+          "fabind_layernorm_fwd")
+    return y, mean, rstd
+
+
+def layernorm_bwd(x, w, dy, mean, rstd):
+    """Adjoint of layernorm_fwd -> (dx, dw, db)."""
+    R, C = x.shape
+    dx = torch.empty_like(x)
+    nb = (R + 3) // 4
+    dwp = torch.empty((nb, C), dtype=torch.float32, device=x.device)
+    dbp = torch.empty((nb, C), dtype=torch.float32, device=x.device)
+    check(_lib.load().fabind_layernorm_bwd(ptr(x), ptr(w), ptr(dy), ptr(mean), ptr(rstd), R, C, ptr(dx), ptr(dwp), ptr(dbp),
+                                           stream()), "fabind_layernorm_bwd")
+    return dx, colsum(dwp), colsum(dbp)
+
+
+def layernorm_rows_bwd(x, w, dy, eps=1e-5):
+    """Adjoint of layernorm_rows (any dtype / leading dimension) -> (dx, dw, db)."""
+    R, C = x.shape
+    C8 = (C + 7) // 8 * 8                               # rows padded to 8 elements: the adjoint kernel's 16-byte accesses (csrc/norm.hip)
+    dx = torch.empty((R, C8), dtype=x.dtype, device=x.device)[:, :C]
+    nblk = max(1, min((R + 3) // 4, 2048))              # work-groups of four waves, rows strided over them: 8 per CU
+    dwp = torch.empty((nblk, C), dtype=torch.float32, device=x.device)
+    dbp = torch.empty((nblk, C), dtype=torch.float32, device=x.device)
+    check(_lib.load().fabind_layernorm_rows_bwd(ptr(x), dt_code(x.dtype), _ld(x), ptr(w), ptr(dy), dt_code(dy.dtype), _ld(dy), eps, R, C,
+                                                ptr(dx), dt_code(dx.dtype), C8, ptr(dwp), ptr(dbp), nblk, stream()),
+          "fabind_layernorm_rows_bwd")
+    return dx, colsum(dwp), colsum(dbp)
+
+
+def edge_concat(h, row, col, rhohat, out_dtype, pad_to):
+    """[h[row] | h[col] | rhohat | 0...] per edge -> [E, pad_to]."""
+    E, H = row.shape[0], h.shape[1]
+    y = torch.empty((E, pad_to), dtype=out_dtype, device=h.device)
+    check(_lib.load().fabind_edge_concat(ptr(h), _ld(h), H, ptr(row), ptr(col), ptr(rhohat), E, ptr(y), dt_code(out_dtype), pad_to,
+                                         pad_to, stream()), "fabind_edge_concat")
+    return y
+
+
+def pocket_center_fwd(logits, mask_u8, xyz, noise, tau, hard):
+    """The Gumbel-softmax pocket centre (csrc/heads.hip) -> (center [B, 3], wsum [B])."""
+    B, L = logits.shape
+    center = torch.empty((B, 3), dtype=torch.float32, device=logits.device)
+    wsum = torch.empty(B, dtype=torch.float32, device=logits.device)
+    check(_lib.load().fabind_pocket_center_fwd(ptr(logits), ptr(mask_u8), ptr(xyz), ptr(noise), B, L, float(tau), int(bool(hard)),
+                                               ptr(center), ptr(wsum), stream()), "fabind_pocket_center_fwd")
+    return center, wsum
+
+
+def pocket_center_bwd(logits, mask_u8, xyz, noise, tau, center, wsum, dcenter):
+    """Adjoint of pocket_center_fwd to the logits."""
+    B, L = logits.shape
+    dlogits = torch.empty_like(logits)
+    check(_lib.load().fabind_pocket_center_bwd(ptr(logits), ptr(mask_u8), ptr(xyz), ptr(noise), B, L, tau, ptr(center), ptr(wsum),
+                                               ptr(dcenter), ptr(dlogits), stream()), "fabind_pocket_center_bwd")
+    return dlogits
+
+
+LOSS_TICKET = {}          # (device, stream) -> the arrival counter of loss_fwd's last-block reduction (two streams must not share one)
+
+
+def loss_fwd(coords, coords_true, y_pred, y_by, dis_map, logits, cls, cls_dt, mask_u8, center, center_true, w):
+    """The six-term training loss in one launch (csrc/heads.hip) -> (loss scalar, terms [6], out [8]: what loss_bwd reads).
+    w: dict(coord, pair, distill, cls, center, delta) of floats."""
+    lib = _lib.load()
+    dev = coords.device
+    key = (dev, stream())
+    tk = LOSS_TICKET.get(key)
+    if tk is None:
+        tk = LOSS_TICKET[key] = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_pair, n_coord, n_cls, n_center = y_pred.numel(), coords.numel(), logits.numel(), center.numel()
+    part = torch.empty((lib.fabind_loss_blocks(n_pair, n_coord, n_cls), 8), dtype=torch.float32, device=dev)
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    terms = torch.empty(6, dtype=torch.float32, device=dev)
+    check(lib.fabind_loss_fwd(ptr(coords), ptr(coords_true), n_coord, ptr(y_pred), ptr(y_by), ptr(dis_map), n_pair, ptr(logits),
+                              ptr(cls), cls_dt, ptr(mask_u8), n_cls, ptr(center), ptr(center_true), n_center, w['coord'], w['pair'],
+                              w['distill'], w['cls'], w['center'], w['delta'], ptr(part), ptr(tk), ptr(out), ptr(loss), ptr(terms),
+                              stream()), "fabind_loss_fwd")
+    return loss, terms, out
+
+
+def loss_bwd(coords, coords_true, y_pred, y_by, dis_map, logits, cls, cls_dt, center, center_true, w, out, g_loss, g_terms, d):
+    """The five gradient seeds of loss_fwd into d = [d coords, d y_pred, d y_by, d logits, d center] (None: not wanted)."""
+    check(_lib.load().fabind_loss_bwd(ptr(coords), ptr(coords_true), coords.numel(), ptr(y_pred), ptr(y_by), ptr(dis_map), y_pred.numel(),
+                                      ptr(logits), ptr(cls), cls_dt, logits.numel(), ptr(center), ptr(center_true), center.numel(),
+                                      w['coord'], w['pair'], w['distill'], w['cls'], w['center'], w['delta'], ptr(out), ptr(g_loss),
+                                      ptr(g_terms), ptr(d[0]), ptr(d[1]), ptr(d[2]), ptr(d[3]), ptr(d[4]), stream()), "fabind_loss_bwd")
+
+
+def pair_dist_fwd(bl, xp, xc, scale, lo, hi):
+    """clamp(scale * |xp_i - xc_j|, lo, hi) over the dense per-complex pair blocks `bl` -> fp32 [pairs]."""
+    y = torch.empty(bl.n_pairs, dtype=torch.float32, device=xc.device)
+    check(_lib.load().fabind_pair_dist_fwd(bl.desc_ptr, bl.B, bl.n_tiles, ptr(xp), ptr(xc), scale, lo, hi, ptr(y), stream()),
+          "fabind_pair_dist_fwd")
+    return y
+
+
+def pair_dist_bwd(bl, xp, xc, dy, scale, lo, hi):
+    """Adjoint of pair_dist_fwd to xc as a fixed-order sum."""
+    part = torch.empty((bl.B, 8, bl.max_C, 3), dtype=torch.float32, device=xc.device)
+    dxc = torch.empty_like(xc)
+    check(_lib.load().fabind_pair_dist_bwd(bl.desc_ptr, bl.B, bl.max_C, ptr(xp), ptr(xc), ptr(dy), scale, lo, hi, ptr(part), ptr(dxc),
+                                           stream()), "fabind_pair_dist_bwd")
+    return dxc
+
+
+def lower_bound(a, keys, n_keys):
+    """out[k] = first position of the sorted int32 vector `a` whose value is >= keys[k] -> int32 [n_keys]."""
+    out = torch.empty(n_keys, dtype=torch.int32, device=a.device)
+    check(_lib.load().fabind_lower_bound(ptr(a), a.numel(), ptr(keys), n_keys, ptr(out), stream()), "fabind_lower_bound")
+    return out
+
+
+def pose_stats(p, t, aoff, B):
+    """(rmsd [B], centroid distance [B]) of the atoms [aoff[b], aoff[b + 1]) of the fp32 [N, 3] coordinates p against t."""
+    rmsd = torch.empty(B, dtype=torch.float32, device=p.device)
+    cdis = torch.empty_like(rmsd)
+    check(_lib.load().fabind_pose_stats(ptr(p), ptr(t), ptr(aoff), B, ptr(rmsd), ptr(cdis), stream()), "fabind_pose_stats")
+    return rmsd, cdis
+
+
+def rank_loss_fwd(scores, rmsd, group_off, G, mode, with_ce):
+    """The pairwise ranking loss per group (csrc/ranking.hip) -> (terms [G, 3], d terms / d scores, counts int32 [G, 4])."""
+    terms = torch.empty((G, 3), dtype=torch.float32, device=scores.device)
+    counts = torch.empty((G, 4), dtype=torch.int32, device=scores.device)
+    d_scores = torch.empty_like(scores)
+    check(_lib.load().fabind_rank_loss_fwd(ptr(scores), ptr(rmsd), ptr(group_off), G, mode, int(with_ce), ptr(terms), ptr(d_scores),
+                                           ptr(counts), stream()), "fabind_rank_loss_fwd")
+    return terms, d_scores, counts

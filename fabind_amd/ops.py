@@ -3,14 +3,11 @@
 Forward-only calls (torch.no_grad(), 7 of the 8 refinement iterations) go straight to the kernels;
 when a gradient is required the same kernels run inside torch.autograd.Function wrappers whose
 backward passes are HIP kernels as well (fabind_amd/csrc/bwd.hip + the GEMM family)."""
-import ctypes
-
 import numpy as np
 import torch
 
 from . import config as _cfg
 from . import kernels as K
-from ._lib import GemmArgs, check, dt_code, load, ptr, stream
 
 
 def act_dtype():
@@ -28,26 +25,11 @@ def needs_grad(*ts):
 _needs_grad = needs_grad
 
 
-def _nchunk(rows):
-    return max(1, min(1024, (rows + 255) // 256))
-
-
 def _ksplit(R):
     """(splits, padded K) for a contraction over R rows (weight gradients: tiny M x N, huge K)."""
     S = max(1, min(128, R // 4096))
     unit = 64 * S
     return S, (R + unit - 1) // unit * unit
-
-
-def _transposed(x, Rp):
-    """x^T as an mm-dtype [C, Rp] matrix (zero padded) for K=R contractions."""
-    R, C = x.shape
-    out = torch.empty((C, Rp), dtype=mm_dtype(), device=x.device)
-    if Rp != R:
-        out[:, R:].zero_()
-    check(load().fabind_transpose_act(ptr(x), dt_code(x.dtype), x.stride(0), ptr(out), dt_code(out.dtype), Rp, R, C, K.ACT_NONE,
-                                      stream()), "fabind_transpose_act")
-    return out
 
 
 FUSE_DB_TN = _cfg.knob("FABIND_FUSE_DB_TN")   # bias gradients ride along with the TN weight-gradient contraction
@@ -131,9 +113,10 @@ def _weight_grad(dpre, x, x2, W, want_db):
         dW, db = _tn(dpre, x, x2, W, with_db)
     else:
         S, Rp = _ksplit(dpre.shape[0])
-        dpt, xt = _transposed(dpre, Rp), _transposed(x, Rp)
+        md = mm_dtype()
+        dpt, xt = K.transpose_act(dpre, Rp, md), K.transpose_act(x, Rp, md)      # zero-padded transposes: operands of K = R contractions
         if x2 is not None:
-            xt = torch.cat([xt, _transposed(x2, Rp)], 0)
+            xt = torch.cat([xt, K.transpose_act(x2, Rp, md)], 0)
         if S == 1:
             dW = K.gemm(dpt, xt)[0]
         else:
@@ -161,12 +144,7 @@ def _param_grads(dpre, x, x2, W, want_dW, want_db, db=None):
 # Under autograd the kernel also emits act_epi'(pre-activation) (SiLU) so that backward is a plain multiply,
 # and fp32 activations are fed to the MFMA kernels as bf16 copies in bf16 mode (also what is saved).
 # ------------------------------------------------------------------------------------------------
-def _mul_dact(dy, aux, act, out_dtype, scale=1.0):
-    out = torch.empty(dy.shape, dtype=out_dtype, device=dy.device)
-    a = aux if aux is not None else dy
-    check(load().fabind_mul_dact(ptr(dy), dt_code(dy.dtype), ptr(a), dt_code(a.dtype), act, ptr(out), dt_code(out_dtype),
-                                 dy.numel(), float(scale), stream()), "fabind_mul_dact")
-    return out
+_mul_dact, _mul_dact_colsum, _mul_dropmask_colsum, _rowdot_bwd = K.mul_dact, K.mul_dact_colsum, K.mul_dropmask_colsum, K.rowdot_bwd
 
 
 DB_IN_TN_ROWS = 32768
@@ -178,31 +156,6 @@ def _db_in_tn(dy):
     sums cost the queued contraction nothing visible; on large ones the fused pass is the cheaper place (its partials are free next
     to 300 MB of traffic, the contraction's VALU slots are not)."""
     return K.TN_DEFER and dy.shape[0] <= DB_IN_TN_ROWS and dy.dtype in (torch.float32, torch.bfloat16) and mm_dtype() == torch.bfloat16
-
-
-def _mul_dact_colsum(dy, aux, act, out_dtype, scale=1.0):
-    """(scale * dy * act'(aux), its column sums) in one pass (bias gradient fused into the activation adjoint / cast)."""
-    R, C = dy.shape
-    out = torch.empty((R, C), dtype=out_dtype, device=dy.device)
-    nchunk = max(1, min(4096, (R + 63) // 64))           # >= 2 blocks per SIMD at C = 512: the pass is latency-bound
-    scratch = torch.empty((nchunk, C), dtype=torch.float32, device=dy.device)
-    db = torch.empty(C, dtype=torch.float32, device=dy.device)
-    check(load().fabind_mul_dact_colsum(ptr(dy), dt_code(dy.dtype), ptr(aux), dt_code(aux.dtype) if aux is not None else 0,
-                                        act, ptr(out), dt_code(out_dtype), R, C, ptr(db), ptr(scratch), nchunk, float(scale), stream()),
-          "fabind_mul_dact_colsum")
-    return out, db
-
-
-def _mul_dropmask_colsum(dy, p_drop, seed, out_dtype):
-    """(dy * keep(seed, r, c) / (1 - p), its column sums): the adjoint of a GEMM epilogue's dropout with the mask regenerated from its key."""
-    R, C = dy.shape
-    out = torch.empty((R, C), dtype=out_dtype, device=dy.device)
-    nchunk = max(1, min(4096, (R + 63) // 64))
-    scratch = torch.empty((nchunk, C), dtype=torch.float32, device=dy.device)
-    db = torch.empty(C, dtype=torch.float32, device=dy.device)
-    check(load().fabind_mul_dropmask_colsum(ptr(dy), dt_code(dy.dtype), ptr(out), dt_code(out_dtype), R, C, float(p_drop), int(seed) & 0xFFFFFFFF,
-                                            ptr(db), ptr(scratch), nchunk, stream()), "fabind_mul_dropmask_colsum")
-    return out, db
 
 
 def _dpre_plan(dy, act, drop, want_db, want_dW):
@@ -597,41 +550,11 @@ def mlp2_relu(x, W1, b1, W2, b2, last_act, residual=None, out_dtype=torch.float3
 # linear + row-dot:  s_part[m, t] = sum_{n in tile t} act_epi(act_pro(x) W^T + b)[m,n] * u[n]
 # ------------------------------------------------------------------------------------------------
 def _gemm_rowdot(x, W, b, u, act_pro, act_epi, store, p_drop=0.0, seed=0, fold=None, post=False):
-    """GEMM with row-dot epilogue; store=True keeps the pre-activation matrix (training) -- or, with post=True, the activation's
-    output after the epilogue dropout.  fold = (row_mu, row_rs, col_c): LayerNorm of the rows of x folded into the epilogue (inference)."""
-    M, Kd = x.shape
-    N = W.shape[0]
-    nt = (N + K.GEMM_BN - 1) // K.GEMM_BN
-    part = torch.empty((M, nt), dtype=torch.float32, device=x.device)
-    z = torch.empty((M, N), dtype=act_dtype(), device=x.device) if store else None
-    a = GemmArgs()
-    a.A, a.W, a.C, a.bias, a.dotvec, a.dot_out = ptr(x), ptr(W), ptr(z), ptr(b), ptr(u), ptr(part)
-    a.M, a.N, a.K, a.K1 = M, N, Kd, Kd
-    a.lda, a.ldw, a.ldc, a.dot_ld = x.stride(0), W.stride(0), N, nt
-    a.a_dtype, a.w_dtype, a.c_dtype = dt_code(x.dtype), dt_code(W.dtype), dt_code(z.dtype) if store else 0
-    a.act_pro, a.act_epi, a.store_preact, a.alpha = act_pro, act_epi, (0 if post else 1), 1.0
-    a.p_drop, a.drop_seed = float(p_drop), int(seed) & 0xFFFFFFFF
-    if fold is not None:
-        a.store_preact = 0
-        a.row_mu, a.row_rs, a.col_c = ptr(fold[0]), ptr(fold[1]), ptr(fold[2])
-    x3 = x.dtype == torch.float32 and W.dtype == torch.float32 and _cfg.get_precision() == "bf16x3"
-    a.split3 = 1 if x3 else 0
-    label = "%s <%s,%s%s> M=%d N=%d K=%d" % ("fabind_gemm_x3" if x3 else "fabind_gemm", str(x.dtype).replace("torch.", ""),
-                                             str(W.dtype).replace("torch.", ""), ",x3" if x3 else "", M, N, Kd)
-    K._profiled(label, 2.0 * M * N * Kd, lambda: check(load().fabind_gemm(ctypes.byref(a), stream()), "fabind_gemm(rowdot)"))
-    return z, part
-
-
-def _rowdot_bwd(z, dpart, u, act_epi):
-    """Adjoint of part = row-dot(act_epi(z), u) over the stored z -> (dz = dpart u act_epi'(z) as z.dtype, du fp32); dpart [M, tiles] contiguous."""
-    M, N = z.shape
-    dz = torch.empty_like(z)
-    nchunk = _nchunk(M)
-    scratch = torch.empty((nchunk, N), dtype=torch.float32, device=z.device)
-    du = torch.empty(N, dtype=torch.float32, device=z.device)
-    check(load().fabind_rowdot_bwd(ptr(z), dt_code(z.dtype), ptr(dpart), dpart.shape[1], ptr(u), act_epi, M, N,
-                                   ptr(dz), ptr(du), ptr(scratch), nchunk, stream()), "fabind_rowdot_bwd")
-    return dz, du
+    """GEMM with row-dot epilogue -> (z or None, part [M, tiles]); store=True keeps the pre-activation matrix z (training) -- or, with
+    post=True, the activation's output after the epilogue dropout.  fold = (row_mu, row_rs, col_c): LayerNorm of the rows of x folded into
+    the epilogue (inference)."""
+    return K.gemm(x, W, bias=b, act_pro=act_pro, act_epi=act_epi, out_dtype=act_dtype(), want_out=store, dotvec=u, ldc=W.shape[0], k_splits=0,
+                  p_drop=p_drop, seed=seed, store_preact=not post and fold is None, fold=fold, nbytes=0.0)
 
 
 class _LinearRowdot(torch.autograd.Function):
@@ -737,6 +660,26 @@ EDGE_SAVE_MIN_H = 256
 #  headline and 1,371 / 1,342 against 1,326 / 1,335 on the production-shape model step, two interleaved pairs each (profiles/r06_ab_same_box.txt))
 
 
+def _fused_edge_bwd(ctx, dagg, ds, x3, frags):
+    """The backward of both fused edge nodes -> the gradients of their eight tensor inputs.  x3 (_FusedEdgeX3): the bf16 kernels on a bf16
+    copy of the fp32 AB rows, fp32 gradients throughout."""
+    AB, rhohat, w_r, W2, b2, Wc, bc, w3 = ctx.saved_tensors[:8]
+    saved = tuple(ctx.saved_tensors[8:]) if ctx.n_saved else None
+    g = ctx.g
+    colptr, perm = g.ctx_by_col()
+    if dagg is None:
+        dagg = torch.zeros((AB.shape[0], ctx.H), dtype=torch.float32, device=AB.device)
+    if ds is None:
+        ds = torch.zeros(g.row_ctx.shape[0], dtype=torch.float32, device=AB.device)
+    dAB, drh, dwr, dW2, db2, dWc, dbc, dw3 = K.gcl_edge_fused_bwd(
+        AB.to(torch.bfloat16) if x3 else AB, ctx.H, g.row_ctx, g.col_ctx, rhohat, w_r, W2, b2, Wc, bc, w3, ds.reshape(-1).float(), dagg.float(),
+        colptr, perm, ctx.p_drop, ctx.seed, dab_bf16=not x3 and AB.dtype == torch.bfloat16, w_dtype=torch.float32 if x3 else W2.dtype,
+        rowptr=g.rp_ctx, frags=frags, saved=saved)
+    if x3:
+        return dAB, drh, dwr, dW2, db2, dWc, dbc, dw3
+    return dAB.to(AB.dtype), drh, dwr, dW2.to(W2.dtype), db2, dWc.to(Wc.dtype), dbc, dw3
+
+
 class _FusedEdge(torch.autograd.Function):
     """Whole intra-graph edge pipeline of MC_E_GCL as one kernel each way (csrc/fused_edge.hip).  H >= 256 (EDGE_SAVE_MIN_H): the training forward leaves the messages and two bf16 per-edge tiles (silu'(pre2), pre3: 6 H bytes per edge
     until the backward has run) and the backward chains two contractions per edge (csrc/fused_edge_bwd4.hip); otherwise -- and with
@@ -758,19 +701,7 @@ class _FusedEdge(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dagg, ds):
-        AB16, rhohat, w_r, W2, b2, Wc, bc, w3 = ctx.saved_tensors[:8]
-        saved = tuple(ctx.saved_tensors[8:]) if ctx.n_saved else None
-        g = ctx.g
-        colptr, perm = g.ctx_by_col()
-        if dagg is None:
-            dagg = torch.zeros((AB16.shape[0], ctx.H), dtype=torch.float32, device=AB16.device)
-        if ds is None:
-            ds = torch.zeros(g.row_ctx.shape[0], dtype=torch.float32, device=AB16.device)
-        dAB, drh, dwr, dW2, db2, dWc, dbc, dw3 = K.gcl_edge_fused_bwd(
-            AB16, ctx.H, g.row_ctx, g.col_ctx, rhohat, w_r, W2, b2, Wc, bc, w3, ds.reshape(-1).float(), dagg.float(),
-            colptr, perm, ctx.p_drop, ctx.seed, dab_bf16=AB16.dtype == torch.bfloat16, w_dtype=W2.dtype, rowptr=g.rp_ctx, frags=ctx.frags,
-            saved=saved)
-        return (dAB.to(AB16.dtype), drh, dwr, dW2.to(W2.dtype), db2, dWc.to(Wc.dtype), dbc, dw3, None, None, None, None, None, None)
+        return _fused_edge_bwd(ctx, dagg, ds, False, ctx.frags) + (None, None, None, None, None, None)
 
 
 class _FusedEdgeX3(torch.autograd.Function):
@@ -794,18 +725,7 @@ class _FusedEdgeX3(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dagg, ds):
-        AB, rhohat, w_r, W2, b2, Wc, bc, w3 = ctx.saved_tensors[:8]
-        saved = tuple(ctx.saved_tensors[8:]) if ctx.n_saved else None
-        g = ctx.g
-        colptr, perm = g.ctx_by_col()
-        if dagg is None:
-            dagg = torch.zeros((AB.shape[0], ctx.H), dtype=torch.float32, device=AB.device)
-        if ds is None:
-            ds = torch.zeros(g.row_ctx.shape[0], dtype=torch.float32, device=AB.device)
-        dAB, drh, dwr, dW2, db2, dWc, dbc, dw3 = K.gcl_edge_fused_bwd(
-            AB.to(torch.bfloat16), ctx.H, g.row_ctx, g.col_ctx, rhohat, w_r, W2, b2, Wc, bc, w3, ds.reshape(-1).float(), dagg.float(),
-            colptr, perm, ctx.p_drop, ctx.seed, dab_bf16=False, w_dtype=torch.float32, rowptr=g.rp_ctx, saved=saved)
-        return (dAB, drh, dwr, dW2, db2, dWc, dbc, dw3, None, None, None, None)
+        return _fused_edge_bwd(ctx, dagg, ds, True, None) + (None, None, None, None)
 
 
 def fused_edge(AB16, rhohat, w_r, W2, b2, Wc, bc, w3, H, g, p_drop=0.0, frags=None):
@@ -855,7 +775,7 @@ class _EdgeGeom(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dd, drhohat):
         row, col, rowptr, d, rho, norm = ctx.saved_tensors
-        lay, E, dev = ctx.lay, row.shape[0], d.device
+        lay, dev = ctx.lay, d.device
         if ctx.bycol is not None:
             colptr, perm = ctx.bycol()
         else:                                     # edges grouped by sending node (index glue, no activations)
@@ -863,15 +783,9 @@ class _EdgeGeom(torch.autograd.Function):
             colptr = torch.zeros(ctx.n + 1, dtype=torch.int32, device=dev)
             colptr[1:] = torch.cumsum(torch.bincount(colsorted, minlength=ctx.n), 0).to(torch.int32)
             perm = perm64.to(torch.int32)
-        dx = torch.empty((ctx.n, 3), dtype=torch.float32, device=dev)
         dd = dd.contiguous() if dd is not None else torch.zeros_like(d)
         drhohat = drhohat.contiguous() if drhohat is not None else torch.zeros_like(rho)
-        gbuf = torch.empty((max(E, 1), 3), dtype=torch.float32, device=dev)
-        check(load().fabind_edge_geom_bwd(ptr(d), ptr(rho), ptr(norm), ptr(dd), ptr(drhohat), ptr(row), ptr(rowptr),
-                                          ptr(colptr), ptr(perm), ptr(lay.node_off), lay.B, E, ctx.n, ptr(dx), ptr(gbuf),
-                                          ptr(torch.empty(lay.B, dtype=torch.float32, device=dev)), stream()),
-              "fabind_edge_geom_bwd")
-        return dx, None, None, None, None, None
+        return K.edge_geom_bwd(d, rho, norm, dd, drhohat, row, rowptr, colptr, perm, lay.node_off, lay.B, ctx.n), None, None, None, None, None
 
 
 def edge_geom(x, row, col, rowptr, lay, bycol=None):
@@ -898,19 +812,14 @@ class _GclPre(torch.autograd.Function):
     def backward(ctx, dout):
         AB, rhohat, w_r, D = ctx.saved_tensors
         H, g = ctx.H, ctx.g
-        E, N = g.row_ctx.shape[0], AB.shape[0]
+        N = AB.shape[0]
         dout = dout.contiguous()
         dpre = dout if D is None else _mul_dact(dout, D, K.ACT_STORED_DERIV, dout.dtype)
         dAB = torch.empty((N, 2 * H), dtype=torch.float32, device=AB.device)
         K.segment_sum(dpre, g.rp_ctx, N, out=dAB[:, :H])                      # receiving side: rows are CSR segments
         colptr, perm = g.ctx_by_col()
         K.segment_sum(dpre, colptr, N, eidx=perm, out=dAB[:, H:])             # sending side: permuted segments
-        drh = torch.empty(E, dtype=torch.float32, device=AB.device)
-        nchunk = max(1, min(2048, (E + 255) // 256))
-        scratch = torch.empty((nchunk, H), dtype=torch.float32, device=AB.device)
-        dw = torch.empty(H, dtype=torch.float32, device=AB.device)
-        check(load().fabind_gcl_pre_bwd(ptr(dpre), dt_code(dpre.dtype), H, ptr(rhohat), ptr(w_r), E, ptr(drh), ptr(dw),
-                                        ptr(scratch), nchunk, stream()), "fabind_gcl_pre_bwd")
+        drh, dw = K.gcl_pre_bwd(dpre, H, rhohat, w_r)
         return dAB, drh, dw, None, None, None
 
 
@@ -930,11 +839,7 @@ class _SegmentSum(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         Z, row = ctx.saved_tensors
-        dout = dout.contiguous()
-        dZ = torch.empty_like(Z)
-        check(load().fabind_gather_dact(ptr(dout), dout.stride(0), ptr(row), ptr(Z), dt_code(Z.dtype), ctx.act, ptr(dZ),
-                                        dt_code(dZ.dtype), Z.shape[0], Z.shape[1], stream()), "fabind_gather_dact")
-        return dZ, None, None, None, None
+        return K.gather_dact(dout.contiguous(), row, Z, ctx.act), None, None, None, None
 
 
 def segment_sum(Z, rowptr, row, n_rows, act=K.ACT_NONE):
@@ -955,12 +860,8 @@ class _CoordUpdate(torch.autograd.Function):
     def backward(ctx, dxo):
         d, s, rowptr = ctx.saved_tensors
         dxo = dxo.contiguous()
-        E = s.shape[0]
-        dd = torch.empty((E, 3), dtype=torch.float32, device=d.device)
-        ds = torch.empty(E, dtype=torch.float32, device=d.device)
-        check(load().fabind_coord_update_bwd(ptr(d), ptr(s), ptr(rowptr), dxo.shape[0], 1 if ctx.mean else 0, ctx.clampv,
-                                             ptr(dxo), ptr(dd), ptr(ds), stream()), "fabind_coord_update_bwd")
-        return dxo, dd, ds[:, None].expand(E, ctx.np), None, None, None
+        dd, ds = K.coord_update_bwd(d, s, rowptr, dxo, ctx.mean, ctx.clampv)
+        return dxo, dd, ds[:, None].expand(s.shape[0], ctx.np), None, None, None
 
 
 def coord_update(x, d, s_part, rowptr, mean, clampv):
@@ -1039,16 +940,12 @@ class _DropMix(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, hn, p_drop, seed):
-        out = torch.empty_like(h)
-        check(load().fabind_drop_mix(ptr(h), ptr(hn), ptr(out), h.numel(), float(p_drop), int(seed) & 0xFFFFFFFF, stream()), "fabind_drop_mix")
         ctx.pd, ctx.seed = float(p_drop), int(seed)
-        return out
+        return K.drop_mix(h, hn, p_drop, seed)
 
     @staticmethod
     def backward(ctx, g):
-        g = g.contiguous()
-        dhn, dh = torch.empty_like(g), torch.empty_like(g)
-        check(load().fabind_drop_mix_bwd(ptr(g), ptr(dhn), ptr(dh), g.numel(), ctx.pd, ctx.seed & 0xFFFFFFFF, stream()), "fabind_drop_mix_bwd")
+        dhn, dh = K.drop_mix_bwd(g.contiguous(), ctx.pd, ctx.seed)
         return dh, dhn, None, None
 
 
@@ -1061,9 +958,7 @@ def drop_mix(h, hn, p_drop):
         seed = _drop_seed(p_drop)
         if _needs_grad(h, hn):
             return _DropMix.apply(h, hn, p_drop, seed)
-        out = torch.empty_like(h)
-        check(load().fabind_drop_mix(ptr(h), ptr(hn), ptr(out), h.numel(), float(p_drop), seed, stream()), "fabind_drop_mix")
-        return out
+        return K.drop_mix(h, hn, p_drop, seed)
     return h + torch.nn.functional.dropout(hn - h, p_drop, True)
 
 
@@ -1356,14 +1251,7 @@ class _CrossAttn(torch.autograd.Function):
         dqg, dkv = torch.zeros_like(qg), torch.zeros_like(kv)                                  # uncovered rows: 0
         # pass Q writes both 16-B segments of every pair the descriptors cover; with an 8-column bias tensor that is all of it
         dbias = torch.empty_like(bias) if (bias.shape[1] == 8 and lin_col == 0 and gate_col == 4 and ctx.covers_all) else torch.zeros_like(bias)
-        dO = torch.empty((qg.shape[0], 128), dtype=torch.float32, device=qg.device)
-        Dv = torch.empty((qg.shape[0], 4), dtype=torch.float32, device=qg.device)
-        n_scr = int(load().fabind_cross_attn_bwd_scratch(B, max_nq, max_nk))     # per-split partials of the short side (or 0)
-        scr = torch.empty(n_scr, dtype=torch.float32, device=qg.device) if n_scr else None
-        fn = load().fabind_cross_attn_mfma_bwd if ctx.mfma else load().fabind_cross_attn_bwd
-        check(fn(ptr(qg), qg.stride(0), ptr(kv), kv.stride(0), ptr(bias), bias.stride(0), lin_col, gate_col, ptr(desc), B, max_nq,
-                 max_nk, scale, ptr(out), ptr(lse), ptr(dout), ptr(dqg), ptr(dkv), ptr(dbias), ptr(dO), ptr(Dv), ptr(scr), stream()),
-              "fabind_cross_attn_bwd")
+        K.cross_attn_bwd(qg, kv, bias, lin_col, gate_col, desc, B, max_nq, max_nk, scale, out, lse, dout, dqg, dkv, dbias, ctx.mfma)
         return dqg, dkv, dbias, None, None, None, None, None, None, None
 
 
@@ -1399,15 +1287,10 @@ class _PairHadamard(torch.autograd.Function):
                 and H <= 1024 and H2 <= 256
                 and dhd.stride(0) % 4 == 0):
             # the pairs are the inter graph's own rows: one wave per node, one writer per element, fixed order (no float atomics)
-            check(load().fabind_pair_hadamard_bwd_rows(
-                ptr(dhd), dt_code(dhd.dtype), dhd.stride(0), ptr(T0), T0.stride(0), H, ptr(T1), T1.stride(0), H2, ptr(g.rp_int),
-                ptr(g.col_int), ptr(g.red_idx), ptr(red_c), T0.shape[0], ptr(d0), d0.stride(0), ptr(d1), d1.stride(0), stream()),
-                "fabind_pair_hadamard_bwd_rows")
+            K.pair_hadamard_bwd_rows(dhd, T0, H, T1, H2, g.rp_int, g.col_int, g.red_idx, red_c, d0, d1)
             return d0_ret, d1, None, None, None, None, None
-        check(load().fabind_pair_hadamard_bwd(
-            ptr(dhd), dt_code(dhd.dtype), dhd.stride(0), ptr(T0[:, :H]), ptr(T0[:, H:]), T0.stride(0), H, ptr(T1[:, :H2]),
-            ptr(T1[:, H2:]), T1.stride(0), H2, ptr(red_p), ptr(red_c), red_p.shape[0], ptr(d0[:, :H]), ptr(d0[:, H:]),
-            d0.stride(0), ptr(d1[:, :H2]), ptr(d1[:, H2:]), d1.stride(0), stream()), "fabind_pair_hadamard_bwd")
+        K.pair_hadamard_bwd(dhd, T0[:, :H], T0[:, H:], H, T1[:, :H2], T1[:, H2:], H2, red_p, red_c,
+                            d0[:, :H], d0[:, H:], d1[:, :H2], d1[:, H2:])
         return d0_ret, d1, None, None, None, None, None
 
 
@@ -1428,11 +1311,7 @@ class _RowsHadamard(torch.autograd.Function):
     def forward(ctx, t, ia, ib, a_sorted=False, blocks=None, n_a=0):
         ctx.save_for_backward(t, ia, ib)
         ctx.a_sorted, ctx.blocks, ctx.n_a = a_sorted, blocks, n_a
-        fwd = _block_hadamard_fwd(t, blocks, n_a)
-        if fwd is not None:
-            return fwd
-        dummy = t[:, :0]
-        return K.pair_hadamard(t, t, dummy, dummy, ia, ib, act_dtype())
+        return _rows_hadamard_fwd(t, ia, ib, blocks, n_a)
 
     @staticmethod
     def backward(ctx, dout):
@@ -1443,27 +1322,14 @@ class _RowsHadamard(torch.autograd.Function):
         if bl is not None and dout.dtype == torch.bfloat16 and t.dtype == torch.float32 and W in (64, 128, 256, 512) and t.stride(0) % 2 == 0 \
                 and ctx.n_a == bl.n_prows and t.shape[0] == bl.n_prows + bl.n_crows and dout.shape[0] == bl.n_pairs:
             # round 6: the pairs are dense per-complex blocks -> one pass over dout (read once), d t rows written once each, no per-call CSR
-            dt_ = torch.empty_like(t)
-            part = torch.empty((bl.n_tiles, bl.nchunk_max, bl.chunk, W), dtype=torch.float32, device=t.device)
-            tc, dtc = t[ctx.n_a:], dt_[ctx.n_a:]
-            check(load().fabind_block_hadamard_bwd(bl.desc_ptr, bl.B, bl.n_tiles, ptr(dout), dout.stride(0), ptr(t), t.stride(0), ptr(tc),
-                                                   t.stride(0), W, bl.row_b_ptr, bl.n_crows, bl.nchunk_max, ptr(part), ptr(dt_),
-                                                   dt_.stride(0), ptr(dtc), dt_.stride(0), stream()), "fabind_block_hadamard_bwd")
-            return dt_, None, None, None, None, None
+            return K.block_hadamard_bwd(bl, dout, t, ctx.n_a), None, None, None, None, None
         if ROWS_HADAMARD_WALK and t.dtype == torch.float32 and W % 4 == 0 and W <= 1024 and t.stride(0) % 4 == 0 and dout.stride(0) % 4 == 0:
             # every row of t gets its pairs as a CSR: as first factor (the pairs sorted by ia) and as second factor (sorted by ib);
             # one wave per row sums them -- no float atomics, fixed order (index glue: two stable sorts and two histograms per call)
-            n = t.shape[0]
-            rowptr, pair_idx, partner = _rows_hadamard_csr(ia, ib, n, ctx.a_sorted)
-            dt_ = torch.empty_like(t)
-            check(load().fabind_rows_hadamard_bwd(ptr(dout), dt_code(dout.dtype), dout.stride(0), ptr(t), t.stride(0), W,
-                                                  ptr(rowptr), ptr(pair_idx), ptr(partner), n, ptr(dt_), dt_.stride(0),
-                                                  stream()), "fabind_rows_hadamard_bwd")
-            return dt_, None, None, None, None, None
+            rowptr, pair_idx, partner = _rows_hadamard_csr(ia, ib, t.shape[0], ctx.a_sorted)
+            return K.rows_hadamard_bwd(dout, t, rowptr, pair_idx, partner), None, None, None, None, None
         dt_ = torch.zeros_like(t)
-        check(load().fabind_pair_hadamard_bwd(ptr(dout), dt_code(dout.dtype), dout.stride(0), ptr(t), ptr(t), t.stride(0), W,
-                                              None, None, 0, 0, ptr(ia), ptr(ib), ia.shape[0], ptr(dt_), ptr(dt_),
-                                              dt_.stride(0), None, None, 0, stream()), "fabind_pair_hadamard_bwd")
+        K.pair_hadamard_bwd(dout, t, t, W, None, None, 0, ia, ib, dt_, dt_, None, None)
         return dt_, None, None, None, None, None
 
 
@@ -1503,10 +1369,15 @@ def _block_hadamard_fwd(t, bl, n_a):
     if not (bl is not None and act_dtype() == torch.bfloat16 and t.dtype == torch.float32 and W in (64, 128, 256, 512) and t.stride(1) == 1
             and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 and n_a == bl.n_prows and t.shape[0] == bl.n_prows + bl.n_crows and n_a % 4 == 0):
         return None
-    out = torch.empty((bl.n_pairs, W), dtype=torch.bfloat16, device=t.device)
-    check(load().fabind_block_hadamard_fwd(bl.desc_ptr, bl.B, bl.n_tiles, ptr(t), t.stride(0), ptr(t[n_a:]), t.stride(0), W, ptr(out), W,
-                                           stream()), "fabind_block_hadamard_fwd")
-    return out
+    return K.block_hadamard_fwd(bl, t, n_a)
+
+
+def _rows_hadamard_fwd(t, ia, ib, blocks, n_a):
+    fwd = _block_hadamard_fwd(t, blocks, n_a)
+    if fwd is not None:
+        return fwd
+    dummy = t[:, :0]
+    return K.pair_hadamard(t, t, dummy, dummy, ia, ib, act_dtype())
 
 
 def rows_hadamard(t, idx_a, idx_b, a_sorted=False, blocks=None, n_a=0):
@@ -1516,11 +1387,7 @@ def rows_hadamard(t, idx_a, idx_b, a_sorted=False, blocks=None, n_a=0):
     ia, ib = idx_a.to(torch.int32).contiguous(), idx_b.to(torch.int32).contiguous()
     if _needs_grad(t):
         return _RowsHadamard.apply(t, ia, ib, a_sorted, blocks, n_a)
-    fwd = _block_hadamard_fwd(t, blocks, n_a)
-    if fwd is not None:
-        return fwd
-    dummy = t[:, :0]
-    return K.pair_hadamard(t, t, dummy, dummy, ia, ib, act_dtype())
+    return _rows_hadamard_fwd(t, ia, ib, blocks, n_a)
 
 
 class _InterAttn(torch.autograd.Function):
@@ -1553,39 +1420,15 @@ class _InterAttn(torch.autograd.Function):
     def backward(ctx, dh_out, dx_out, _dalpha):
         qkv, cv, d, rhohat, w_rk, w_rv, wcr, w3, alpha, cvs, v_in, Wc = ctx.saved_tensors
         g, H = ctx.g, ctx.H
-        N, E = qkv.shape[0], g.col_int.shape[0]
-        dev = qkv.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        dh_out = dh_out.contiguous() if dh_out is not None else torch.zeros((N, H), **f32)
-        dx_out = dx_out.contiguous() if dx_out is not None else torch.zeros((N, 3), **f32)
-        dqkv = torch.empty_like(qkv)          # every row is written: d q by pass a (zeros for nodes without inter edges), d k | d v by pass b
-        dcv = torch.empty_like(cv)
-        # (pass a writes d d, d rhohat, d logit and d cp of EVERY edge -- each edge lies in one row's range: no pre-zeroing)
-        dd, drh = torch.empty((max(E, 1), 3), **f32), torch.empty(max(E, 1), **f32)
-        n_red = E // 2
-        dbias_red = torch.zeros(max(n_red, 1), **f32)
-        dlogit, dcp = torch.empty(max(E, 1), **f32), torch.empty(max(E, 1), **f32)
-        if E == 0:
-            dd.zero_(); drh.zero_()
+        N, dev = qkv.shape[0], qkv.device
+        dh_out = dh_out.contiguous() if dh_out is not None else torch.zeros((N, H), dtype=torch.float32, device=dev)
+        dx_out = dx_out.contiguous() if dx_out is not None else torch.zeros((N, 3), dtype=torch.float32, device=dev)
         # (pass a strides its waves over the rows; 7 % of the rows hold all the edges, but the draw is not what bounds it: 1,024 / 2,048 /
         #  4,096 work-groups measured 1,034 / 1,035 / 1,088 us forward + backward at the bench shape, tools/probes/inter_attn_time.py)
         nblk = min((N + 3) // 4, INTER_BWD_BLOCKS)
-        wpart = torch.empty((nblk, 4 * H), **f32)                     # [block][4][H] partials of the four vector gradients
         deal = getattr(g, "int_deal", None) if K.INTER_ATTN_ROWS else None
-        if deal is not None:             # the rows dealt by degree: heavy rows on four waves (csrc/inter_attn_rows.hip)
-            check(load().fabind_inter_attn_bwd_rows(ptr(qkv), qkv.stride(0), ptr(cv), cv.stride(0), H, ptr(d), ptr(rhohat),
-                                                    ptr(g.rp_int), ptr(g.col_int), ptr(g.mirror), ptr(g.red_idx), ptr(w_rk),
-                                                    ptr(w_rv), ptr(wcr), ptr(w3), ptr(alpha), ptr(cvs), ctx.clampv, N, ptr(dh_out),
-                                                    ptr(dx_out), ptr(dqkv), ptr(dcv), ptr(dd), ptr(drh), ptr(dbias_red), ptr(dlogit),
-                                                    ptr(dcp), ptr(wpart), nblk, ptr(deal[0]), int(deal[1]), int(deal[2]), stream()),
-                  "fabind_inter_attn_bwd_rows")
-        else:
-            check(load().fabind_inter_attn_bwd(ptr(qkv), qkv.stride(0), ptr(cv), cv.stride(0), H, ptr(d), ptr(rhohat),
-                                               ptr(g.rp_int), ptr(g.col_int), ptr(g.mirror), ptr(g.red_idx), ptr(w_rk),
-                                               ptr(w_rv), ptr(wcr), ptr(w3), ptr(alpha), ptr(cvs), ctx.clampv, N, ptr(dh_out),
-                                               ptr(dx_out), ptr(dqkv), ptr(dcv), ptr(dd), ptr(drh), ptr(dbias_red), ptr(dlogit),
-                                               ptr(dcp), ptr(wpart), nblk, stream()), "fabind_inter_attn_bwd")
-        dw_all = K.colsum(wpart)                                      # one launch pair for all four
+        dqkv, dcv, dd, drh, dbias_red, dcp, dw_all = K.inter_attn_bwd(qkv, cv, H, d, rhohat, g.rp_int, g.col_int, g.mirror, g.red_idx, w_rk, w_rv,
+                                                                      wcr, w3, alpha, cvs, ctx.clampv, dh_out, dx_out, nblk, deal)
         dw = [dw_all[i * H:(i + 1) * H] for i in range(4)]
         dWc = dbc = None
         if ctx.has_cv:                                               # adjoint of cv = V Wc^T + bc, dV added to dqkv[:, 2H:]
@@ -1596,8 +1439,8 @@ class _InterAttn(torch.autograd.Function):
             dcv = None
         if ctx.sink_h is not None and ctx.needs_input_grad[2]:
             dh_out = ctx.sink_h.deposit(dh_out)           # h_out = h + ...: the residual gradient joins h's shared buffer
-        return (dqkv, dcv, dh_out, dx_out, dd[:E], drh[:E], dbias_red[:n_red, None].expand(n_red, ctx.np), dw[0], dw[1],
-                dw[2], dw[3], None, None, None, dcp[:E] if ctx.has_ext else None, dWc, dbc, None, None)
+        return (dqkv, dcv, dh_out, dx_out, dd, drh, dbias_red[:, None].expand(dbias_red.shape[0], ctx.np), dw[0], dw[1],
+                dw[2], dw[3], None, None, None, dcp if ctx.has_ext else None, dWc, dbc, None, None)
 
 
 INTER_BWD_BLOCKS = 1024
@@ -1645,12 +1488,8 @@ class _LasStep(torch.autograd.Function):
     def backward(ctx, dout):
         x, x0, mask = ctx.saved_tensors
         las, lay = ctx.las, ctx.lay
-        dout = dout.contiguous()
-        dx = torch.empty_like(x)
-        check(load().fabind_las_step_bwd(ptr(x), ptr(x0), ptr(mask), ptr(las[0]), ptr(las[1]), ptr(las[2]),
-                                         ptr(lay.node_off), ptr(lay.c_cnt), lay.B, lay.max_n, ctx.step, ctx.clampv,
-                                         ptr(dout), ptr(dx), stream()), "fabind_las_step_bwd")
-        return dx, None, None, None, None, None
+        return K.las_step_bwd(x, x0, mask, las[0], las[1], las[2], lay.node_off, lay.c_cnt, lay.B, lay.max_n, ctx.step, ctx.clampv,
+                              dout.contiguous()), None, None, None, None, None
 
 
 def las_step(x, x0, las, lay, step, clampv):
@@ -1709,6 +1548,31 @@ def _pair_bias_groups(lay, H, ld_ab, nblk, Kp):
     return lay._pbg
 
 
+def _pair_bias_adjoint_tail(lay, H, a0b0, a16, da0b0, Acat, BTcat, wrows, ran, Kp):
+    """What the two pair-bias adjoints (_PairBias, _CrossAttnFused) share once the bf16 gradient rows of all blocks lie K-concatenated in
+    Acat and the b0 * w operand in BTcat: d a0 of ALL blocks as ONE accumulating ragged GEMM into da0b0; then, per block that ran,
+    T_k = D_k^T a0 on the pipelined NT kernel (K-major, uniformly padded copies of both operands: one batched transpose each) and the
+    finishing pass (d b0 into da0b0, d w partials per group of 16 ligand-side nodes, all blocks side by side) -> d w [nblk, 8, H] by
+    one column sum: fixed order, no float atomics anywhere on this path.  a16: bf16 rows whose first H columns are a0; wrows [nblk, 8, H]:
+    the weight rows in the caller's order; ran: the blocks that have a gradient."""
+    nblk, NO = wrows.shape[0], 8
+    cat_g, t_g = _pair_bias_groups(lay, H, a0b0.stride(0), nblk, Kp)
+    K.gemm(Acat, BTcat, out=da0b0, accumulate=True, groups=cat_g, n_groups=lay.B, max_m=lay.max_P, max_n=H,
+           M=lay.sumP, N=lay.B * H, ldc=a0b0.stride(0), flops=2.0 * lay.n_pairs * NO * nblk * H)
+    Pp = (lay.max_P + 63) // 64 * 64          # K of the T contractions: a multiple of 64 selects the LDS-DMA pipelined kernel
+    Dt = K.batched_transpose_pad(Acat, lay.desc_p, lay.B, nblk, Kp, Pp)
+    At = K.batched_transpose_pad(a16, lay.desc_pf, lay.B, 1, H, Pp)[0]
+    # (a block that did not run leaves its columns of the partials unwritten: zeros then)
+    fin = (torch.empty if len(ran) == nblk else torch.zeros)((K.pair_bias_finish_parts(lay.sumC), nblk * NO * H), dtype=torch.float32,
+                                                             device=a0b0.device)
+    T = torch.empty((lay.sumC * NO, H), dtype=torch.float32, device=a0b0.device)
+    for k in ran:
+        K.gemm(Dt[k], At, out=T, groups=t_g, n_groups=lay.B, max_m=lay.max_C * NO, max_n=H, M=lay.B * Kp, N=lay.B * H, ldc=H,
+               flops=2.0 * lay.n_pairs * NO * H)
+        K.pair_bias_finish(T, a0b0, H, wrows[k], lay.c_index, lay.sumC, da0b0, fin[:, k * NO * H:])
+    return K.colsum(fin).view(nblk, NO, H)
+
+
 class _PairBias(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a0b0, wcomp, bconst, H, lay):
@@ -1722,10 +1586,9 @@ class _PairBias(torch.autograd.Function):
         a0b0, wcomp = ctx.saved_tensors
         H, lay = ctx.H, ctx.lay
         nblk, NO, _ = wcomp.shape
-        dev = a0b0.device
         da0b0, da0b0_ret = _sink_zeros(a0b0, ctx.sink)    # every writer below accumulates (+=, accumulating GEMM, atomics)
         dwcomp = None
-        dbconst = torch.zeros((nblk, NO), dtype=torch.float32, device=dev)
+        dbconst = torch.zeros((nblk, NO), dtype=torch.float32, device=a0b0.device)
         # ('bf16x3': the adjoint of the pair-bias contraction takes the bf16 route too -- see _x3_tn_ok; FABIND_X3_PAIRBIAS_BWD=fp32
         #  restores the fp32 atomics kernels, 30 ms per step at the headline shape)
         mode = _cfg.get_precision()
@@ -1735,55 +1598,20 @@ class _PairBias(torch.autograd.Function):
             # the matching b0 * wcomp operand (BTcat) -> d a0 is ONE plain-group GEMM on the pipelined kernel (one accumulating
             # epilogue pass over the strided fp32 gradient instead of one per block); T_k = D_k^T a0 reads column slice k
             Kp = (lay.max_C * NO + 31) // 32 * 32
-            cat_g, t_g = _pair_bias_groups(lay, H, a0b0.stride(0), nblk, Kp)
             a16 = a0b0.to(torch.bfloat16)
-            T = torch.empty((lay.sumC * NO, H), dtype=torch.float32, device=dev)
-            ds = [None if d is None else d.contiguous() for d in douts]
-            Acat = torch.empty((lay.sumP, nblk * Kp), dtype=torch.bfloat16, device=dev)
-            BTcat = torch.empty((lay.B * H, nblk * Kp), dtype=torch.bfloat16, device=dev)
-            ptrs = (ctypes.c_void_p * nblk)(*[None if d is None else d.data_ptr() for d in ds])
-            wc = wcomp.contiguous()
-            n_part = int(load().fabind_pair_bias_cat_parts(lay.B, lay.max_P))
-            colpart = torch.empty((n_part, nblk * NO), dtype=torch.float32, device=dev)   # per-work-group column sums of the douts
-            check(load().fabind_pair_bias_cat(ptrs, nblk, ptr(lay.desc_p), lay.B, lay.max_P, Kp, ptr(Acat), Acat.stride(0),
-                                              ptr(a0b0[:, H:]), a0b0.stride(0), ptr(lay.c_index), ptr(wc), H, ptr(BTcat),
-                                              BTcat.stride(0), ptr(colpart), stream()), "fabind_pair_bias_cat")
+            Acat, BTcat, colpart = K.pair_bias_cat([None if d is None else d.contiguous() for d in douts], lay, H, Kp, a0b0[:, H:],
+                                                   wcomp.contiguous())
             dbconst = K.colsum(colpart).reshape(nblk, NO)                                  # = column sums of every dout_k
-            K.gemm(Acat, BTcat, out=da0b0, accumulate=True, groups=cat_g, n_groups=lay.B, max_m=lay.max_P, max_n=H,
-                   M=lay.sumP, N=lay.B * H, ldc=a0b0.stride(0), flops=2.0 * lay.n_pairs * NO * nblk * H)
-            # the T_k = D_k^T a0 contractions on the pipelined NT kernel: K-major, uniformly padded copies of both operands
-            Pp = (lay.max_P + 63) // 64 * 64          # K of these contractions: a multiple of 64 selects the LDS-DMA pipelined kernel
-            Dt = torch.empty((nblk, lay.B * Kp, Pp), dtype=torch.bfloat16, device=dev)
-            At = torch.empty((lay.B * H, Pp), dtype=torch.bfloat16, device=dev)
-            check(load().fabind_batched_transpose_pad(ptr(Acat), Acat.stride(0), ptr(lay.desc_p), lay.B, nblk, Kp, Pp, ptr(Dt),
-                                                      stream()), "fabind_batched_transpose_pad")
-            check(load().fabind_batched_transpose_pad(ptr(a16), a16.stride(0), ptr(lay.desc_pf), lay.B, 1, H, Pp, ptr(At), stream()),
-                  "fabind_batched_transpose_pad")
-            # per-group partials of every block's d wcomp side by side: [groups of 16 ligand-side nodes, nblk * 8 * H] -> one column sum
-            n_fin = int(load().fabind_pair_bias_finish_parts(lay.sumC))
-            fin = (torch.empty if all(d is not None for d in douts) else torch.zeros)((n_fin, nblk * NO * H), dtype=torch.float32, device=dev)
+            dwcomp = _pair_bias_adjoint_tail(lay, H, a0b0, a16, da0b0, Acat, BTcat, wcomp, [k for k, d in enumerate(douts) if d is not None], Kp)
+            return da0b0_ret, dwcomp, dbconst, None, None
         for k, dout in enumerate(douts):
             if dout is None:
                 continue
             dout = dout.contiguous()
-            if not bf16:
-                dbconst[k] = K.colsum(dout)
-            if bf16:
-                K.gemm(Dt[k], At, out=T, groups=t_g, n_groups=lay.B, max_m=lay.max_C * NO, max_n=H, M=lay.B * Kp, N=lay.B * H, ldc=H,
-                       flops=2.0 * lay.n_pairs * NO * H)
-                check(load().fabind_pair_bias_finish(ptr(T), ptr(a0b0), a0b0.stride(0), H, ptr(wcomp[k]), ptr(lay.c_index),
-                                                     lay.sumC, ptr(da0b0), ptr(fin[:, k * NO * H:]), fin.stride(0), stream()),
-                      "fabind_pair_bias_finish")
-            else:
-                if dwcomp is None:
-                    dwcomp = torch.zeros_like(wcomp)
-                dwk = torch.zeros((lay.B, NO * H), dtype=torch.float32, device=dev)
-                check(load().fabind_pair_bias_bwd(ptr(dout), NO, ptr(a0b0), a0b0.stride(0), H, ptr(wcomp[k]), ptr(lay.desc_p),
-                                                  lay.B, lay.max_P, lay.max_C, ptr(lay.p_index), ptr(lay.c_index), ptr(da0b0),
-                                                  ptr(dwk), stream()), "fabind_pair_bias_bwd")
-                dwcomp[k] = K.colsum(dwk).reshape(NO, H)
-        if bf16:
-            dwcomp = K.colsum(fin).view(nblk, NO, H)           # fixed order: no float atomics anywhere on this path
+            dbconst[k] = K.colsum(dout)
+            if dwcomp is None:
+                dwcomp = torch.zeros_like(wcomp)
+            dwcomp[k] = K.colsum(K.pair_bias_bwd(dout, NO, a0b0, H, wcomp[k], lay, da0b0)).reshape(NO, H)
         return da0b0_ret, dwcomp, dbconst, None, None
 
 
@@ -1881,7 +1709,7 @@ class _CrossAttnFused(torch.autograd.Function):
         bw = pb._bw
         if bw is None:                       # first block of this backward pass: the state the blocks share
             Kp = (lay.max_C * NO + 31) // 32 * 32
-            n_tiles = int(load().fabind_cross_attn_fused_bwd_parts(lay.B, lay.max_P))
+            n_tiles = K.cross_attn_fused_bwd_parts(lay.B, lay.max_P)
             bw = pb._bw = dict(Kp=Kp, left=pb._n_fused, done=[],
                                acat=torch.empty((lay.sumP, nblk * Kp), dtype=torch.bfloat16, device=dev),
                                colpart=torch.zeros((n_tiles, nblk * NO), dtype=torch.float32, device=dev))
@@ -1901,8 +1729,6 @@ class _CrossAttnFused(torch.autograd.Function):
             # D_k[i, (j, slot)] a0[i, h] over ALL rows of a complex -- one batched transpose of the bf16 gradient rows, one ragged GEMM and
             # one finishing pass per block, one column sum for all weight gradients and one for all constants -- and hands the shared
             # gradients to autograd.
-            Pp = (lay.max_P + 63) // 64 * 64
-            cat_g, t_g = _pair_bias_groups(lay, H, a0b0.stride(0), nblk, Kp)
             acat = bw["acat"]
             wslot = wcomp.float()[:, _SLOT_TO_ROW].contiguous()              # [nblk, 8, H], rows in the packed operands' slot order
             ran = sorted(bw["done"])
@@ -1910,27 +1736,10 @@ class _CrossAttnFused(torch.autograd.Function):
             if len(ran) != nblk:
                 for kk in set(range(nblk)) - set(ran):
                     acat[:, kk * Kp:(kk + 1) * Kp].zero_()
-            BTcat = torch.empty((lay.B * H, nblk * Kp), dtype=torch.bfloat16, device=dev)
-            check(load().fabind_pair_bias_btcat(ptr(a0b0[:, H:]), a0b0.stride(0), ptr(lay.c_index), ptr(lay.desc_p), ptr(wslot), nblk, H, Kp,
-                                                ptr(BTcat), BTcat.stride(0), lay.B, stream()), "fabind_pair_bias_btcat")
-            K.gemm(acat, BTcat, out=da0b0, accumulate=True, groups=cat_g, n_groups=lay.B, max_m=lay.max_P, max_n=H,
-                   M=lay.sumP, N=lay.B * H, ldc=a0b0.stride(0), flops=2.0 * lay.n_pairs * NO * nblk * H)
-            Dt = torch.empty((nblk, lay.B * Kp, Pp), dtype=torch.bfloat16, device=dev)
-            At = torch.empty((lay.B * H, Pp), dtype=torch.bfloat16, device=dev)
-            check(load().fabind_batched_transpose_pad(ptr(acat), acat.stride(0), ptr(lay.desc_p), lay.B, nblk, Kp, Pp, ptr(Dt), stream()),
-                  "fabind_batched_transpose_pad")
-            check(load().fabind_batched_transpose_pad(ptr(a16), a16.stride(0), ptr(lay.desc_pf), lay.B, 1, H, Pp, ptr(At), stream()),
-                  "fabind_batched_transpose_pad")
-            n_fin = int(load().fabind_pair_bias_finish_parts(lay.sumC))
-            fin = (torch.empty if len(ran) == nblk else torch.zeros)((n_fin, nblk * NO * H), dtype=torch.float32, device=dev)
-            T = torch.empty((lay.sumC * NO, H), dtype=torch.float32, device=dev)
-            for kk in ran:
-                K.gemm(Dt[kk], At, out=T, groups=t_g, n_groups=lay.B, max_m=lay.max_C * NO, max_n=H, M=lay.B * Kp, N=lay.B * H, ldc=H,
-                       flops=2.0 * lay.n_pairs * NO * H)
-                check(load().fabind_pair_bias_finish(ptr(T), ptr(a0b0), a0b0.stride(0), H, ptr(wslot[kk]), ptr(lay.c_index), lay.sumC,
-                                                     ptr(da0b0), ptr(fin[:, kk * NO * H:]), fin.stride(0), stream()), "fabind_pair_bias_finish")
+            BTcat = K.pair_bias_btcat(a0b0[:, H:], lay, wslot, H, Kp)
+            dw_slot = _pair_bias_adjoint_tail(lay, H, a0b0, a16, da0b0, acat, BTcat, wslot, ran, Kp)
             inv = [_SLOT_TO_ROW.index(r_) for r_ in range(NO)]              # wcomp / bconst row -> slot
-            dw_ret = K.colsum(fin).view(nblk, NO, H)[:, inv].contiguous().to(wcomp.dtype)
+            dw_ret = dw_slot[:, inv].contiguous().to(wcomp.dtype)
             db_ret = K.colsum(bw["colpart"]).view(nblk, NO)[:, inv].contiguous()
             pb._bw = None
             pb._fused_blocks.clear()                  # the pass is complete: the context may serve another one (_n_fused stays: a second
@@ -1955,8 +1764,7 @@ def cross_attn_fused_train(qg, kv, pb, k_blk, mode, scale):
 def cross_attn_fused(qg, kv, pb, k_blk, mode, lay, scale):
     """Forward-only gated cross attention of block k_blk with the pair bias recomputed in the kernel (csrc/attn_mfma.hip)."""
     a16, bo, bc = pb.fused(k_blk)
-    out = torch.zeros((qg.shape[0], 128), dtype=torch.float32, device=qg.device) if mode == 0 else \
-        torch.empty((qg.shape[0], 128), dtype=torch.float32, device=qg.device)
+    out = (torch.zeros if mode == 0 else torch.empty)((qg.shape[0], 128), dtype=torch.float32, device=qg.device)      # rows outside every block: 0
     return K.cross_attn_fused_fwd(qg[:, :128], kv[:, :128], kv[:, 128:], qg[:, 128:], a16, bo, bc, lay, pb.H, mode, scale, out)
 
 
@@ -1966,27 +1774,14 @@ def cross_attn_fused(qg, kv, pb, k_blk, mode, lay, scale):
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, eps):
-        R, C = x.shape
-        y = torch.empty_like(x)
-        mean = torch.empty(R, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(R, dtype=torch.float32, device=x.device)
-        check(load().fabind_layernorm_fwd(ptr(x), ptr(w), ptr(b), eps, R, C, ptr(y), ptr(mean), ptr(rstd), stream()),
-              "fabind_layernorm_fwd")
+        y, mean, rstd = K.layernorm_fwd(x, w, b, eps)
         ctx.save_for_backward(x, w, mean, rstd)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, mean, rstd = ctx.saved_tensors
-        R, C = x.shape
-        dy = dy.contiguous()
-        dx = torch.empty_like(x)
-        nb = (R + 3) // 4
-        dwp = torch.empty((nb, C), dtype=torch.float32, device=x.device)
-        dbp = torch.empty((nb, C), dtype=torch.float32, device=x.device)
-        check(load().fabind_layernorm_bwd(ptr(x), ptr(w), ptr(dy), ptr(mean), ptr(rstd), R, C, ptr(dx), ptr(dwp), ptr(dbp),
-                                          stream()), "fabind_layernorm_bwd")
-        return dx, K.colsum(dwp), K.colsum(dbp), None
+        return K.layernorm_bwd(x, w, dy.contiguous(), mean, rstd) + (None,)
 
 
 def layernorm(x, w, b, eps=1e-5):
@@ -2000,11 +1795,7 @@ def layernorm(x, w, b, eps=1e-5):
 class _PocketCenter(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, mask_u8, xyz, noise, tau, hard):
-        B, L = logits.shape
-        center = torch.empty((B, 3), dtype=torch.float32, device=logits.device)
-        wsum = torch.empty(B, dtype=torch.float32, device=logits.device)
-        check(load().fabind_pocket_center_fwd(ptr(logits), ptr(mask_u8), ptr(xyz), ptr(noise), B, L, float(tau), int(bool(hard)),
-                                              ptr(center), ptr(wsum), stream()), "fabind_pocket_center_fwd")
+        center, wsum = K.pocket_center_fwd(logits, mask_u8, xyz, noise, tau, hard)
         ctx.save_for_backward(logits, mask_u8, xyz, noise if noise is not None else logits.new_empty(0), center, wsum)
         ctx.tau, ctx.has_noise = float(tau), noise is not None
         return center
@@ -2012,12 +1803,8 @@ class _PocketCenter(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dcenter):
         logits, mask_u8, xyz, noise, center, wsum = ctx.saved_tensors
-        B, L = logits.shape
-        dlogits = torch.empty_like(logits)
-        check(load().fabind_pocket_center_bwd(ptr(logits), ptr(mask_u8), ptr(xyz), ptr(noise) if ctx.has_noise else None, B, L, ctx.tau,
-                                              ptr(center), ptr(wsum), ptr(dcenter.contiguous().float()), ptr(dlogits), stream()),
-              "fabind_pocket_center_bwd")
-        return dlogits, None, None, None, None, None
+        return K.pocket_center_bwd(logits, mask_u8, xyz, noise if ctx.has_noise else None, ctx.tau, center, wsum,
+                                   dcenter.contiguous().float()), None, None, None, None, None
 
 
 def pocket_center(logits, mask, xyz, tau=1.0, hard=False, noise=None):
@@ -2028,7 +1815,7 @@ def pocket_center(logits, mask, xyz, tau=1.0, hard=False, noise=None):
     return _PocketCenter.apply(lg, m8, xyz.float().contiguous(), None if noise is None else noise.float().contiguous(), tau, hard)
 
 
-_LOSS_TICKET = {}
+_LOSS_TICKET = K.LOSS_TICKET
 _CLS_DT = {torch.float32: 0, torch.int64: 1, torch.int32: 2, torch.uint8: 3, torch.bool: 3}
 LOSS_TERM_NAMES = ("pocket_cls", "pocket_center", "contact", "contact_by_pred", "distill", "coord")
 
@@ -2036,22 +1823,8 @@ LOSS_TERM_NAMES = ("pocket_cls", "pocket_center", "contact", "contact_by_pred", 
 class _SixTermLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, coords, y_pred, y_by, logits, center, coords_true, dis_map, cls, mask_u8, center_true, w):
-        dev = coords.device
-        key = (dev, stream())                      # (one arrival counter per device AND stream: two streams must not share it)
-        tk = _LOSS_TICKET.get(key)
-        if tk is None:
-            tk = _LOSS_TICKET[key] = torch.zeros(1, dtype=torch.int32, device=dev)
-        n_pair, n_coord, n_cls, n_center = y_pred.numel(), coords.numel(), logits.numel(), center.numel()
-        nblk = load().fabind_loss_blocks(n_pair, n_coord, n_cls)
-        part = torch.empty((nblk, 8), dtype=torch.float32, device=dev)
-        out = torch.empty(8, dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        terms = torch.empty(6, dtype=torch.float32, device=dev)
         cls_dt = _CLS_DT[cls.dtype]
-        check(load().fabind_loss_fwd(ptr(coords), ptr(coords_true), n_coord, ptr(y_pred), ptr(y_by), ptr(dis_map), n_pair, ptr(logits),
-                                     ptr(cls), cls_dt, ptr(mask_u8), n_cls, ptr(center), ptr(center_true), n_center, w['coord'], w['pair'],
-                                     w['distill'], w['cls'], w['center'], w['delta'], ptr(part), ptr(tk), ptr(out), ptr(loss), ptr(terms),
-                                     stream()), "fabind_loss_fwd")
+        loss, terms, out = K.loss_fwd(coords, coords_true, y_pred, y_by, dis_map, logits, cls, cls_dt, mask_u8, center, center_true, w)
         ctx.save_for_backward(coords, y_pred, y_by, logits, center, coords_true, dis_map, cls, center_true, out)
         ctx.w, ctx.cls_dt = w, cls_dt
         return loss, terms
@@ -2059,15 +1832,11 @@ class _SixTermLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_terms):
         coords, y_pred, y_by, logits, center, coords_true, dis_map, cls, center_true, out = ctx.saved_tensors
-        w = ctx.w
         need = ctx.needs_input_grad
         d = [torch.empty_like(t) if need[i] else None for i, t in enumerate((coords, y_pred, y_by, logits, center))]
         gl = None if g_loss is None else g_loss.contiguous().float()
         gt = None if g_terms is None else g_terms.contiguous().float()
-        check(load().fabind_loss_bwd(ptr(coords), ptr(coords_true), coords.numel(), ptr(y_pred), ptr(y_by), ptr(dis_map), y_pred.numel(),
-                                     ptr(logits), ptr(cls), ctx.cls_dt, logits.numel(), ptr(center), ptr(center_true), center.numel(),
-                                     w['coord'], w['pair'], w['distill'], w['cls'], w['center'], w['delta'], ptr(out), ptr(gl), ptr(gt),
-                                     ptr(d[0]), ptr(d[1]), ptr(d[2]), ptr(d[3]), ptr(d[4]), stream()), "fabind_loss_bwd")
+        K.loss_bwd(coords, coords_true, y_pred, y_by, dis_map, logits, cls, ctx.cls_dt, center, center_true, ctx.w, out, gl, gt, d)
         return d[0], d[1], d[2], d[3], d[4], None, None, None, None, None, None
 
 
@@ -2102,7 +1871,7 @@ class PairBlocks:
         from .param_pack import _upload
         kc, nc = np.asarray(kcnt, dtype=np.int64), np.asarray(ncnt, dtype=np.int64)
         B = kc.shape[0]
-        tp, ch = load().fabind_pair_block_tile(), load().fabind_pair_block_chunk()
+        tp, ch = K.pair_block_tile_chunk()
         tiles = (kc + tp - 1) // tp
         d = np.zeros(B, dtype=_PAIRBLOCK)
         d["pair_off"] = np.cumsum(kc * nc) - kc * nc
@@ -2133,22 +1902,14 @@ class PairBlocks:
 class _PairDist(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xp, xc, blocks, scale, lo, hi):
-        y = torch.empty(blocks.n_pairs, dtype=torch.float32, device=xc.device)
-        check(load().fabind_pair_dist_fwd(blocks.desc_ptr, blocks.B, blocks.n_tiles, ptr(xp), ptr(xc), scale, lo, hi, ptr(y), stream()),
-              "fabind_pair_dist_fwd")
         ctx.save_for_backward(xp, xc)
         ctx.blocks, ctx.k = blocks, (scale, lo, hi)
-        return y
+        return K.pair_dist_fwd(blocks, xp, xc, scale, lo, hi)
 
     @staticmethod
     def backward(ctx, dy):
         xp, xc = ctx.saved_tensors
-        bl = ctx.blocks
-        part = torch.empty((bl.B, 8, bl.max_C, 3), dtype=torch.float32, device=xc.device)
-        dxc = torch.empty_like(xc)
-        check(load().fabind_pair_dist_bwd(bl.desc_ptr, bl.B, bl.max_C, ptr(xp), ptr(xc), ptr(dy.contiguous().float()), ctx.k[0], ctx.k[1],
-                                          ctx.k[2], ptr(part), ptr(dxc), stream()), "fabind_pair_dist_bwd")
-        return None, dxc, None, None, None, None
+        return None, K.pair_dist_bwd(ctx.blocks, xp, xc, dy.contiguous().float(), ctx.k[0], ctx.k[1], ctx.k[2]), None, None, None, None
 
 
 def pair_dist(xp, xc, blocks, scale=1.0, lo=0.0, hi=10.0):
@@ -2172,10 +1933,7 @@ COUNT_NAMES = ("ranked_right", "pairs", "hit", "confidence_correct")
 def atom_offsets(compound_batch, B):
     """int32 [B + 1] atom offsets of a sorted per-atom sample id vector, on the device (a binary search per sample: no read-back)."""
     cb = compound_batch.to(torch.int32).contiguous()
-    keys = torch.arange(B + 1, dtype=torch.int32, device=cb.device)
-    out = torch.empty(B + 1, dtype=torch.int32, device=cb.device)
-    check(load().fabind_lower_bound(ptr(cb), cb.numel(), ptr(keys), B + 1, ptr(out), stream()), "fabind_lower_bound")
-    return out
+    return K.lower_bound(cb, torch.arange(B + 1, dtype=torch.int32, device=cb.device), B + 1)
 
 
 def pose_stats(pred, truth, compound_batch, B):
@@ -2188,22 +1946,13 @@ def pose_stats(pred, truth, compound_batch, B):
     if B < 0 or pred.shape[0] >= 2 ** 31 // 3:
         raise ValueError("pose_stats: B >= 0 and fewer than 2^31 / 3 atoms")
     p, t = pred.detach().float().contiguous(), truth.detach().float().contiguous()
-    aoff = atom_offsets(compound_batch, B)
-    rmsd = torch.empty(B, dtype=torch.float32, device=p.device)
-    cdis = torch.empty_like(rmsd)
-    check(load().fabind_pose_stats(ptr(p), ptr(t), ptr(aoff), B, ptr(rmsd), ptr(cdis), stream()), "fabind_pose_stats")
-    return rmsd, cdis
+    return K.pose_stats(p, t, atom_offsets(compound_batch, B), B)
 
 
 class _RankLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scores, rmsd, group_off, G, mode, with_ce):
-        dev = scores.device
-        terms = torch.empty((G, 3), dtype=torch.float32, device=dev)
-        counts = torch.empty((G, 4), dtype=torch.int32, device=dev)
-        d_scores = torch.empty_like(scores)
-        check(load().fabind_rank_loss_fwd(ptr(scores), ptr(rmsd), ptr(group_off), G, mode, int(with_ce), ptr(terms), ptr(d_scores),
-                                          ptr(counts), stream()), "fabind_rank_loss_fwd")
+        terms, d_scores, counts = K.rank_loss_fwd(scores, rmsd, group_off, G, mode, with_ce)
         mean = terms.mean(0)                                       # (ranking, ce, ranking + ce), mean over the groups
         ranking, ce, loss = mean.unbind(0)
         ctx.save_for_backward(d_scores)

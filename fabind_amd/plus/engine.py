@@ -327,17 +327,6 @@ class PairList:
         return out
 
 
-def _pair_hadamard_call(T, Hh, p_node, c_node, out_dtype):
-    """hd[e, :] = T[p_node[e], :Hh] * T[c_node[e], Hh:2Hh]  (InteractionModule's outer product on a pair list)."""
-    from .._lib import check, dt_code, load, ptr, stream
-    n = p_node.shape[0]
-    hd = torch.empty((n, Hh), dtype=out_dtype, device=T.device)
-    a0, b0 = T[:, :Hh], T[:, Hh:2 * Hh]
-    check(load().fabind_pair_hadamard(ptr(a0), ptr(b0), T.stride(0), Hh, ptr(a0), ptr(b0), T.stride(0), 0, ptr(p_node),
-                                      ptr(c_node), n, ptr(hd), dt_code(out_dtype), Hh, stream()), "fabind_pair_hadamard")
-    return hd
-
-
 # ------------------------------------------------------------------------------------------------
 # differentiable pieces specific to the FABind+ data path (the rest comes from fabind_amd.ops)
 # ------------------------------------------------------------------------------------------------
@@ -351,19 +340,8 @@ class _LnRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from .._lib import check, dt_code, load, ptr, stream
         x, w = ctx.saved_tensors
-        R, C = x.shape
-        dy = dy if dy.stride(-1) == 1 else dy.contiguous()
-        C8 = (C + 7) // 8 * 8                               # rows padded to 8 elements: the adjoint kernel's 16-byte accesses (csrc/norm.hip)
-        dx = torch.empty((R, C8), dtype=x.dtype, device=x.device)[:, :C]
-        nblk = max(1, min((R + 3) // 4, 2048))              # work-groups of four waves, rows strided over them: 8 per CU
-        dwp = torch.empty((nblk, C), dtype=torch.float32, device=x.device)
-        dbp = torch.empty((nblk, C), dtype=torch.float32, device=x.device)
-        check(load().fabind_layernorm_rows_bwd(ptr(x), dt_code(x.dtype), x.stride(0), ptr(w), ptr(dy), dt_code(dy.dtype),
-                                               dy.stride(0), 1e-5, R, C, ptr(dx), dt_code(dx.dtype), C8, ptr(dwp), ptr(dbp),
-                                               nblk, stream()), "fabind_layernorm_rows_bwd")
-        return dx, K.colsum(dwp), K.colsum(dbp), None, None
+        return K.layernorm_rows_bwd(x, w, dy if dy.stride(-1) == 1 else dy.contiguous()) + (None, None)
 
 
 def ln_rows(x, w, b, out_dtype, pad_to=None):
@@ -379,14 +357,9 @@ class _EdgeConcat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, rhohat, row, col, rowptr, bycol, out_dtype, pad_to):
-        from .._lib import check, dt_code, load, ptr, stream
-        E, H = row.shape[0], h.shape[1]
-        y = torch.empty((E, pad_to), dtype=out_dtype, device=h.device)
-        check(load().fabind_edge_concat(ptr(h), h.stride(0), H, ptr(row), ptr(col), ptr(rhohat), E, ptr(y), dt_code(out_dtype),
-                                        pad_to, pad_to, stream()), "fabind_edge_concat")
-        ctx.n, ctx.H, ctx.bycol = h.shape[0], H, bycol
+        ctx.n, ctx.H, ctx.bycol = h.shape[0], h.shape[1], bycol
         ctx.save_for_backward(rowptr)
-        return y
+        return K.edge_concat(h, row, col, rhohat, out_dtype, pad_to)
 
     @staticmethod
     def backward(ctx, dy):
@@ -406,11 +379,10 @@ class _PairHad1(torch.autograd.Function):
     def forward(ctx, T, Hh, p_node, c_node, out_dtype, lay=None):
         ctx.Hh, ctx.lay = Hh, lay
         ctx.save_for_backward(T, p_node, c_node)
-        return _pair_hadamard_call(T, Hh, p_node, c_node, out_dtype)
+        return K.pair_hadamard(T[:, :Hh], T[:, Hh:2 * Hh], None, None, p_node, c_node, out_dtype)
 
     @staticmethod
     def backward(ctx, dhd):
-        from .._lib import check, dt_code, load, ptr, stream
         T, p_node, c_node = ctx.saved_tensors
         Hh, lay = ctx.Hh, ctx.lay
         dhd = dhd.contiguous()
@@ -422,16 +394,11 @@ class _PairHad1(torch.autograd.Function):
             if nb is None:
                 nb = lay._node_b = torch.repeat_interleave(torch.arange(lay.B, dtype=torch.int32, device=T.device),
                                                            (lay.node_off[1:] - lay.node_off[:-1]).long(), output_size=lay.N)
-            check(load().fabind_pair_hadamard_bwd_grid(ptr(dhd), dt_code(dhd.dtype), dhd.stride(0), ptr(T), T.stride(0), Hh,
-                                                       ptr(lay.node_off), ptr(lay.c_cnt), ptr(nb), ptr(lay.desc_p), lay.N, ptr(dT),
-                                                       dT.stride(0), stream()), "fabind_pair_hadamard_bwd_grid")
+            K.pair_hadamard_bwd_grid(dhd, T, Hh, lay.node_off, lay.c_cnt, nb, lay.desc_p, lay.N, dT)
             return dT, None, None, None, None, None
         a0, b0 = T[:, :Hh], T[:, Hh:2 * Hh]
         da, db = dT[:, :Hh], dT[:, Hh:2 * Hh]
-        check(load().fabind_pair_hadamard_bwd(ptr(dhd), dt_code(dhd.dtype), dhd.stride(0), ptr(a0), ptr(b0), T.stride(0), Hh,
-                                              ptr(a0), ptr(b0), T.stride(0), 0, ptr(p_node), ptr(c_node), p_node.shape[0], ptr(da),
-                                              ptr(db), dT.stride(0), ptr(da), ptr(db), dT.stride(0), stream()),
-              "fabind_pair_hadamard_bwd")
+        K.pair_hadamard_bwd(dhd, a0, b0, Hh, a0, b0, 0, p_node, c_node, da, db, da, db)      # (no second operand pair: width 0)
         return dT, None, None, None, None, None
 
 
@@ -439,7 +406,7 @@ def pair_had(T, Hh, p_node, c_node, out_dtype, lay=None):
     """lay: the batch layout when (p_node, c_node) is its complete pair list (PairList order) -- selects the atomics-free adjoint."""
     if ops.needs_grad(T):
         return _PairHad1.apply(T, Hh, p_node, c_node, out_dtype, lay)
-    return _pair_hadamard_call(T, Hh, p_node, c_node, out_dtype)
+    return K.pair_hadamard(T[:, :Hh], T[:, Hh:2 * Hh], None, None, p_node, c_node, out_dtype)
 
 
 class _EdgeLnFold(torch.autograd.Function):

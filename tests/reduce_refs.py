@@ -136,17 +136,17 @@ def accum_class(n, U):
 
 
 def nchunk_mul_dact_colsum(R):
-    """ops._mul_dact_colsum / _mul_dropmask_colsum: `nchunk = max(1, min(4096, (R + 63) // 64))`."""
+    """kernels._nchunk_fused (mul_dact_colsum / mul_dropmask_colsum): `max(1, min(4096, (rows + 63) // 64))`."""
     return max(1, min(4096, (R + 63) // 64))
 
 
 def nchunk_gcl_pre(E):
-    """ops._GclPre.backward: `nchunk = max(1, min(2048, (E + 255) // 256))`."""
+    """kernels.gcl_pre_bwd: `nchunk = max(1, min(2048, (E + 255) // 256))`."""
     return max(1, min(2048, (E + 255) // 256))
 
 
 def nchunk_colsum(R):
-    """kernels.colsum and ops._nchunk (rowdot_bwd): `max(1, min(1024, (R + 255) // 256))`."""
+    """kernels._nchunk (colsum, rowdot_bwd): `max(1, min(1024, (rows + 255) // 256))`."""
     return max(1, min(1024, (R + 255) // 256))
 
 

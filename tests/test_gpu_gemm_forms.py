@@ -86,7 +86,7 @@ def _strides(case, n_cols):
 
 
 class _Launch:
-    """Device operands, sentinel-filled outputs and the FabindGemmArgs of one case (built like ops._gemm_rowdot builds its own)."""
+    """Device operands, sentinel-filled outputs and the FabindGemmArgs of one case (built like kernels.gemm builds its own)."""
 
     def __init__(self, case, dev, fill=True):
         from fabind_amd._lib import DT_BF16, DT_F32, GemmArgs

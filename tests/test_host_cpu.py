@@ -699,3 +699,375 @@ def test_param_pack_switch_is_read_at_call_time(monkeypatch):
     assert config.param_pack() == "check"
     monkeypatch.setenv("FABIND_PARAM_PACK", "0")
     assert config.param_pack() == "0"
+
+
+# ------------------------------------------------------------------------------------------------
+# the C ABI is called from kernels.py (and the leaf modules that own a feature); the autograd nodes keep the calculus
+# ------------------------------------------------------------------------------------------------
+_LEAF_MODULES = ("optim.py", "symmetry.py", "conformer.py", "param_pack.py", os.path.join("utils", "generation_utils.py"),
+                 os.path.join("utils", "post_optim_utils.py"))
+# entry points no module of the package calls: development setters / queries and launchers that only tests and tools drive
+_UNCALLED = {"fabind_gemm_plan", "fabind_gcl_edge_fused_bwd_set_tile", "fabind_gcl_edge_fused_bwd_tile", "fabind_gcl_edge_fused_bwd_set_variant",
+             "fabind_gcl_edge_fused_set_variant", "fabind_gcl_edge_fused_variant", "fabind_gcl_edge_fused_bwd_variant", "fabind_pair_bot_pack",
+             "fabind_add"}
+
+
+def test_native_calls_live_in_one_module():
+    """ops.py, engine.py, plus/engine.py and the model modules marshal nothing: no `.fabind_*(` call, no ctypes, none of _lib's marshalling
+    names (imported, or borrowed through `K.`); and every entry point of _lib.SIGNATURES is named by exactly one module of the package."""
+    from fabind_amd import _lib as L
+    users = {n: set() for n in L.SIGNATURES}
+    nodes = 0
+    for rel, src in _package_sources():
+        for n in re.findall(r"\.(fabind_\w+)\b", src):
+            if n in users:
+                users[n].add(rel)
+        if rel in ("ops.py", "engine.py", os.path.join("plus", "engine.py")) or os.path.dirname(rel) in ("models", os.path.join("plus", "models")):
+            nodes += 1
+            assert not re.search(r"\.fabind_\w+\s*\(", src), rel
+            assert not re.search(r"^\s*(import ctypes|from ctypes\b)", src, flags=re.M), rel
+            for m in re.finditer(r"^\s*from\s+\.+_lib\s+import\s+(\([^)]*\)|[^\n]*)", src, flags=re.M):
+                assert not set(re.findall(r"\w+", m.group(1))) & {"GemmArgs", "check", "load", "ptr", "stream", "dt_code"}, (rel, m.group(0))
+            assert not re.search(r"\bK\.(_lib|ptr|check|stream|dt_code|GemmArgs)\b", src), rel
+    assert nodes >= 6
+    for n, files in sorted(users.items()):
+        assert len(files) == (0 if n in _UNCALLED else 1), (n, sorted(files))
+        assert files <= {"kernels.py"} | set(_LEAF_MODULES), (n, sorted(files))
+
+
+class _FakeNative:
+    """Stand-in for the loaded library: every SIGNATURES entry checks its positional arguments against its argtypes -- pointer slots take
+    None or an address handed out by `ptr` / `stream` below, integer slots a Python int that is no such address and fits the type, float
+    slots a number, struct slots a byref whose fields follow the same rule -- and records them; the size queries return small counts."""
+    BASE = 2 ** 40
+    QUERIES = dict(fabind_cross_attn_bwd_scratch=16, fabind_pair_bias_cat_parts=3, fabind_cross_attn_fused_bwd_parts=3,
+                   fabind_pair_bias_finish_parts=2, fabind_loss_blocks=2, fabind_pair_block_tile=64, fabind_pair_block_chunk=4,
+                   fabind_gemm_tn_tile_n=256)
+
+    def __init__(self):
+        self.handed, self.calls = {}, []
+
+    def ptr(self, t):
+        if t is None:
+            return None
+        assert torch.is_tensor(t)
+        key = (t.data_ptr(), t.storage_offset(), tuple(t.shape), tuple(t.stride()), t.dtype)
+        for a, (k, _) in self.handed.items():
+            if k == key:
+                return a
+        a = self.BASE + 4096 * (len(self.handed) + 1)
+        self.handed[a] = (key, t)
+        return a
+
+    def stream(self):
+        a = self.BASE + 1
+        self.handed.setdefault(a, (("stream",), None))
+        return a
+
+    def tensor(self, addr):
+        return self.handed[addr][1]
+
+    def last(self, name):
+        return [a for n, a in self.calls if n == name][-1]
+
+    def _scalar(self, t, v, where):
+        import ctypes
+        if t is ctypes.c_void_p:
+            if isinstance(v, ctypes.Array):                      # the table of block pointers of fabind_pair_bias_cat
+                assert all(e is None or e in self.handed for e in v), where
+            else:
+                assert v is None or (type(v) is int and v in self.handed), (where, v)
+        elif t in (ctypes.c_int, ctypes.c_long, ctypes.c_uint, ctypes.c_longlong):
+            lo, hi = (0, 2 ** 32) if t is ctypes.c_uint else (-2 ** 31, 2 ** 31) if t is ctypes.c_int else (-2 ** 63, 2 ** 63)
+            assert type(v) is int and v not in self.handed and lo <= v < hi, (where, v)
+        elif t is ctypes.c_float:
+            assert type(v) in (int, float), (where, v)
+        else:
+            raise AssertionError("unexpected slot type %r at %s" % (t, where))
+
+    def __getattr__(self, name):
+        import ctypes
+        from fabind_amd import _lib as L
+        if name in self.QUERIES:
+            return lambda *a: self.QUERIES[name]
+        argt = L.SIGNATURES[name]
+
+        def call(*args):
+            assert len(args) == len(argt), (name, len(args), len(argt))
+            rec = []
+            for i, (t, v) in enumerate(zip(argt, args)):
+                if isinstance(t, type) and issubclass(t, ctypes._Pointer) and issubclass(t._type_, ctypes.Structure):
+                    assert type(v) is type(ctypes.byref(ctypes.c_int())) and isinstance(v._obj, t._type_), (name, i)
+                    for f, ft in t._type_._fields_:
+                        self._scalar(ft, getattr(v._obj, f), (name, i, f))
+                    rec.append({f: getattr(v._obj, f) for f, _ in t._type_._fields_})
+                else:
+                    self._scalar(t, v, (name, i))
+                    rec.append(list(v) if isinstance(v, ctypes.Array) else v)
+            self.calls.append((name, rec))
+            return 0
+        return call
+
+
+def test_wrappers_hand_pointers_to_pointer_slots(monkeypatch):
+    """Every wrapper this table of call sites moved into kernels.py, driven once on CPU tensors through _FakeNative: a size or a stride in a
+    pointer slot, a pointer in an integer slot or a wrong argument count fails in the fake; the strides and sizes that arrive are asserted
+    here against operands whose row counts, widths and leading dimensions all differ (5 x 8 views of 5 x 12 buffers and the like), so
+    that a size passed where a stride belongs shows in the recorded value."""
+    from types import SimpleNamespace as NS
+    from fabind_amd import _lib as L, config, ops
+    from fabind_amd import kernels as K
+    fk = _FakeNative()
+    monkeypatch.setattr(L, "load", lambda: fk)
+    monkeypatch.setattr(K, "ptr", fk.ptr)
+    monkeypatch.setattr(K, "stream", fk.stream)
+    monkeypatch.setattr(K, "LOSS_TICKET", {})
+    profiled = []
+    monkeypatch.setattr(K, "_profiled", lambda label, flops, fn, nbytes=0.0, algo=None: (profiled.append((label, flops, nbytes, algo)), fn())[1])
+    f32, bf, i32 = torch.float32, torch.bfloat16, torch.int32
+    A, ST = fk.ptr, fk.stream()
+
+    def v(r, c, ld, dt=f32):
+        return torch.empty((r, ld), dtype=dt)[:, :c]
+
+    def vec(n, dt=f32):
+        return torch.empty(n, dtype=dt)
+
+    def ld_of(addr):
+        return fk.tensor(addr).stride(0)
+
+    # ---- element-wise / reduction adjoints ----
+    x = v(5, 8, 12)
+    out = K.transpose_act(x, 64, bf)
+    a = fk.last("fabind_transpose_act")
+    assert a == [A(x), 0, 12, A(out), 1, 64, 5, 8, K.ACT_NONE, ST] and out.shape == (8, 64)
+    out = K.colsum(x)
+    assert fk.last("fabind_colsum")[:7] == [A(x), 0, 12, A(out), 5, 8, 0] and fk.last("fabind_colsum")[8:] == [1, ST]
+    dy, aux = torch.empty((5, 8)), torch.empty((5, 8), dtype=bf)
+    out = K.mul_dact(dy, aux, K.ACT_RELU, bf, 2.0)
+    assert fk.last("fabind_mul_dact") == [A(dy), 0, A(aux), 1, K.ACT_RELU, A(out), 1, 40, 2.0, ST]
+    out = K.mul_dact(dy, None, K.ACT_NONE, bf)
+    assert fk.last("fabind_mul_dact") == [A(dy), 0, A(dy), 0, K.ACT_NONE, A(out), 1, 40, 1.0, ST]
+    out, db = K.mul_dact_colsum(dy, aux, K.ACT_STORED_DERIV, bf, 0.5)
+    a = fk.last("fabind_mul_dact_colsum")
+    assert a[:10] == [A(dy), 0, A(aux), 1, K.ACT_STORED_DERIV, A(out), 1, 5, 8, A(db)] and a[11:] == [1, 0.5, ST]
+    assert fk.tensor(a[10]).shape == (1, 8) and K._nchunk_fused(5) == 1 and K._nchunk_fused(64 * 4096 + 1) == 4096 and K._nchunk_fused(129) == 3
+    out, db = K.mul_dropmask_colsum(dy, 0.125, 2 ** 32 + 7, bf)
+    a = fk.last("fabind_mul_dropmask_colsum")
+    assert a[:9] == [A(dy), 0, A(out), 1, 5, 8, 0.125, 7, A(db)] and a[10:] == [1, ST]
+    z, dpart, u = torch.empty((5, 8), dtype=bf), torch.empty((5, 3)), vec(8)
+    dz, du = K.rowdot_bwd(z, dpart, u, K.ACT_SILU)
+    a = fk.last("fabind_rowdot_bwd")
+    assert a[:10] == [A(z), 1, A(dpart), 3, A(u), K.ACT_SILU, 5, 8, A(dz), A(du)] and a[11:] == [1, ST] and K._nchunk(257) == 2
+    E, n, B = 7, 5, 2
+    d, rho, norm, row, rowptr, colptr, perm, node_off = torch.empty((E, 3)), vec(E), vec(B), vec(E, i32), vec(n + 1, i32), vec(n + 1, i32), \
+        vec(E, i32), vec(B + 1, i32)
+    dd, drh = torch.empty((E, 3)), vec(E)
+    dx = K.edge_geom_bwd(d, rho, norm, dd, drh, row, rowptr, colptr, perm, node_off, B, n)
+    a = fk.last("fabind_edge_geom_bwd")
+    assert a[:14] == [A(d), A(rho), A(norm), A(dd), A(drh), A(row), A(rowptr), A(colptr), A(perm), A(node_off), B, E, n, A(dx)]
+    assert fk.tensor(a[14]).shape == (E, 3) and fk.tensor(a[15]).shape == (B,) and dx.shape == (n, 3)
+    dpre, w_r = torch.empty((E, 8), dtype=bf), vec(8)
+    drh2, dw = K.gcl_pre_bwd(dpre, 8, rho, w_r)
+    a = fk.last("fabind_gcl_pre_bwd")
+    assert a[:8] == [A(dpre), 1, 8, A(rho), A(w_r), E, A(drh2), A(dw)] and a[9:] == [1, ST] and drh2.shape == (E,) and dw.shape == (8,)
+    dout, Z = v(n, 8, 12), torch.empty((E, 8), dtype=bf)
+    dZ = K.gather_dact(dout, row, Z, K.ACT_SILU)
+    assert fk.last("fabind_gather_dact") == [A(dout), 12, A(row), A(Z), 1, K.ACT_SILU, A(dZ), 1, E, 8, ST]
+    s, dxo = vec(E), torch.empty((n, 3))
+    dd2, ds = K.coord_update_bwd(d, s, rowptr, dxo, True, 0.5)
+    assert fk.last("fabind_coord_update_bwd") == [A(d), A(s), A(rowptr), n, 1, 0.5, A(dxo), A(dd2), A(ds), ST] and dd2.shape == (E, 3)
+    h, hn = torch.empty((5, 8)), torch.empty((5, 8))
+    out = K.drop_mix(h, hn, 0.25, 11)
+    assert fk.last("fabind_drop_mix") == [A(h), A(hn), A(out), 40, 0.25, 11, ST]
+    dhn, dh = K.drop_mix_bwd(h, 0.25, 2 ** 32 + 11)
+    assert fk.last("fabind_drop_mix_bwd") == [A(h), A(dhn), A(dh), 40, 0.25, 11, ST]
+    x0, mask, li, lj, lo, c_cnt = torch.empty((n, 3)), vec(n, torch.uint8), vec(4, i32), vec(4, i32), vec(B + 1, i32), vec(B, i32)
+    dx = K.las_step_bwd(dxo, x0, mask, li, lj, lo, node_off, c_cnt, B, 3, 0.1, 0.5, dxo)
+    assert fk.last("fabind_las_step_bwd") == [A(dxo), A(x0), A(mask), A(li), A(lj), A(lo), A(node_off), A(c_cnt), B, 3, 0.1, 0.5, A(dxo), A(dx), ST]
+    assert K.lower_bound(row, node_off, B + 1).shape == (B + 1,)
+    a = fk.last("fabind_lower_bound")
+    assert a[:4] == [A(row), E, A(node_off), B + 1] and fk.tensor(a[4]).dtype == i32
+
+    # ---- the GEMM's row-dot form: every field of the launch as ops._gemm_rowdot filled it before the wrapper owned it ----
+    xg, Wg, bg, ug = v(5, 8, 12, bf), v(6, 8, 16, bf), vec(6), vec(6)
+    fold = (vec(5), vec(5), vec(6))
+    monkeypatch.setattr(K, "PROFILE", {})
+    prec0 = config.get_precision()
+    try:
+        for mode, dt in (("bf16", bf), ("bf16x3", f32), ("fp32", f32)):
+            config.set_precision(mode)
+            xg, Wg = v(5, 8, 12, dt), v(6, 8, 16, dt)
+            for store, post, fo, p in ((True, False, None, 0.0), (True, True, None, 0.25), (False, False, None, 0.0), (False, False, fold, 0.0)):
+                z, part = ops._gemm_rowdot(xg, Wg, bg, ug, K.ACT_NONE, K.ACT_RELU, store, p_drop=p, seed=2 ** 32 + 3, fold=fo, post=post)
+                g = fk.last("fabind_gemm")[0]
+                x3 = mode == "bf16x3"
+                want = dict.fromkeys(g, 0)
+                want.update({k: None for k, t in L.GemmArgs._fields_ if t is L._vp})
+                want.update(A=A(xg), W=A(Wg), C=A(z), bias=A(bg), dotvec=A(ug), dot_out=A(part), M=5, N=6, K=8, K1=8, lda=12, ldw=16, ldc=6, dot_ld=1,
+                            a_dtype=L.dt_code(dt), w_dtype=L.dt_code(dt), c_dtype=(L.dt_code(z.dtype) if store else 0), act_epi=K.ACT_RELU,
+                            store_preact=(0 if (post or fo is not None) else 1), alpha=1.0, p_drop=p, drop_seed=3, split3=int(x3))
+                if fo is not None:
+                    want.update(row_mu=A(fold[0]), row_rs=A(fold[1]), col_c=A(fold[2]))
+                assert g == want, (mode, store, post, {k: (g[k], want[k]) for k in g if g[k] != want[k]})
+                assert (z is None) == (not store) and part.shape == (5, 1) and (z is None or (z.shape == (5, 6) and z.dtype == ops.act_dtype()))
+                name = str(dt).replace("torch.", "")
+                assert profiled[-1] == ("%s <%s,%s%s> M=5 N=6 K=8" % ("fabind_gemm_x3" if x3 else "fabind_gemm", name, name, ",x3" if x3 else ""),
+                                        2.0 * 5 * 6 * 8, 0.0, None)
+        config.set_precision("bf16")
+        # (the plain form keeps its own figures: k_splits 1, no stored pre-activation, every operand priced once)
+        xg, Wg = v(5, 8, 12, bf), v(6, 8, 16, bf)
+        c, _ = K.gemm(xg, Wg, bias=bg)
+        g = fk.last("fabind_gemm")[0]
+        assert (g["k_splits"], g["store_preact"], g["ldc"], g["lda"], g["ldw"], g["row_mu"], g["dot_out"]) == (1, 0, 6, 12, 16, None, None)
+        assert profiled[-1][2] == 5.0 * 8 * 2 + 6.0 * 8 * 2 + 5.0 * 6 * 4
+    finally:
+        config.set_precision(prec0)
+    monkeypatch.setattr(K, "PROFILE", None)
+
+    # ---- attention and Hadamard adjoints ----
+    qg, kv, bias, desc = v(5, 256, 260), v(6, 256, 264), v(30, 8, 12), torch.empty((B, 8), dtype=i32)
+    o, lse, do_ = torch.empty((5, 128)), torch.empty((5, 4)), torch.empty((5, 128))
+    dqg, dkv, dbias = torch.empty_like(qg), torch.empty_like(kv), torch.empty_like(bias)
+    for mfma, name in ((True, "fabind_cross_attn_mfma_bwd"), (False, "fabind_cross_attn_bwd")):
+        K.cross_attn_bwd(qg, kv, bias, 0, 4, desc, B, 3, 4, 0.125, o, lse, do_, dqg, dkv, dbias, mfma)
+        a = fk.last(name)
+        assert a[:19] == [A(qg), 260, A(kv), 264, A(bias), 12, 0, 4, A(desc), B, 3, 4, 0.125, A(o), A(lse), A(do_), A(dqg), A(dkv), A(dbias)]
+        assert fk.tensor(a[19]).shape == (5, 128) and fk.tensor(a[20]).shape == (5, 4) and fk.tensor(a[21]).shape == (16,) and a[22] == ST
+    T0, T1, rp, rc = torch.empty((5, 20)), torch.empty((5, 12)), vec(E, i32), vec(E, i32)
+    a0, b0, a1, b1 = T0[:, :8], T0[:, 8:16], T1[:, :4], T1[:, 4:8]
+    hd = K.pair_hadamard(a0, b0, a1, b1, rp, rc, bf)
+    assert fk.last("fabind_pair_hadamard") == [A(a0), A(b0), 20, 8, A(a1), A(b1), 12, 4, A(rp), A(rc), E, A(hd), 1, 12, ST] and hd.shape == (E, 12)
+    hd = K.pair_hadamard(a0, b0, None, None, rp, rc, f32)                              # no second pair: the first again, width 0
+    assert fk.last("fabind_pair_hadamard") == [A(a0), A(b0), 20, 8, A(a0), A(b0), 20, 0, A(rp), A(rc), E, A(hd), 0, 8, ST] and hd.shape == (E, 8)
+    dhd, d0, d1 = v(E, 12, 16, bf), torch.empty((5, 24)), torch.empty((5, 28))
+    K.pair_hadamard_bwd(dhd, a0, b0, 8, a1, b1, 4, rp, rc, d0[:, :8], d0[:, 8:16], d1[:, :4], d1[:, 4:8])
+    assert fk.last("fabind_pair_hadamard_bwd") == [A(dhd), 1, 16, A(a0), A(b0), 20, 8, A(a1), A(b1), 12, 4, A(rp), A(rc), E, A(d0[:, :8]),
+                                                   A(d0[:, 8:16]), 24, A(d1[:, :4]), A(d1[:, 4:8]), 28, ST]
+    K.pair_hadamard_bwd(dhd, T0, T0, 20, None, None, 0, rp, rc, d0, d0, None, None)     # ops._RowsHadamard: no second pair at all
+    assert fk.last("fabind_pair_hadamard_bwd") == [A(dhd), 1, 16, A(T0), A(T0), 20, 20, None, None, 0, 0, A(rp), A(rc), E, A(d0), A(d0), 24,
+                                                   None, None, 0, ST]
+    K.pair_hadamard_bwd(dhd, a0, b0, 8, a0, b0, 0, rp, rc, d0[:, :8], d0[:, 8:16], d0[:, :8], d0[:, 8:16])     # plus/engine._PairHad1
+    assert fk.last("fabind_pair_hadamard_bwd")[7:11] == [A(a0), A(b0), 20, 0] and fk.last("fabind_pair_hadamard_bwd")[17:20] == [A(d0[:, :8]), A(d0[:, 8:16]), 24]
+    col, ridx = vec(E, i32), vec(E, i32)
+    K.pair_hadamard_bwd_rows(dhd, T0, 8, T1, 4, rowptr, col, ridx, rc, d0, d1)
+    assert fk.last("fabind_pair_hadamard_bwd_rows") == [A(dhd), 1, 16, A(T0), 20, 8, A(T1), 12, 4, A(rowptr), A(col), A(ridx), A(rc), 5, A(d0), 24,
+                                                        A(d1), 28, ST]
+    nb_, desc_p = vec(5, i32), torch.empty((B, 8), dtype=i32)
+    K.pair_hadamard_bwd_grid(dhd, T0, 8, node_off, c_cnt, nb_, desc_p, 5, d0)
+    assert fk.last("fabind_pair_hadamard_bwd_grid") == [A(dhd), 1, 16, A(T0), 20, 8, A(node_off), A(c_cnt), A(nb_), A(desc_p), 5, A(d0), 24, ST]
+    t, pidx, partner = v(5, 8, 12), vec(2 * E, i32), vec(2 * E, i32)
+    dt_ = K.rows_hadamard_bwd(dhd[:, :8], t, rowptr, pidx, partner)
+    a = fk.last("fabind_rows_hadamard_bwd")
+    assert a == [A(dhd[:, :8]), 1, 16, A(t), 12, 8, A(rowptr), A(pidx), A(partner), 5, A(dt_), dt_.stride(0), ST] and dt_.shape == (5, 8)
+    raw = vec(64, torch.uint8)
+    bl = NS(desc_ptr=A(raw), row_b_ptr=A(raw[32:]), B=B, n_tiles=3, n_pairs=6, n_crows=3, nchunk_max=1, chunk=4)
+    assert K.pair_block_tile_chunk() == (64, 4)
+    o = K.block_hadamard_fwd(bl, t, 2)
+    assert fk.last("fabind_block_hadamard_fwd") == [A(raw), B, 3, A(t), 12, A(t[2:]), 12, 8, A(o), 8, ST] and o.shape == (6, 8) and o.dtype == bf
+    do6 = v(6, 8, 16, bf)
+    dt_ = K.block_hadamard_bwd(bl, do6, t, 2)
+    a = fk.last("fabind_block_hadamard_bwd")
+    assert a[:13] == [A(raw), B, 3, A(do6), 16, A(t), 12, A(t[2:]), 12, 8, A(raw[32:]), 3, 1] and fk.tensor(a[13]).shape == (3, 1, 4, 8)
+    assert a[14:] == [A(dt_), dt_.stride(0), A(dt_[2:]), dt_.stride(0), ST]
+    qkv, cv = v(5, 24, 28), v(5, 8, 12)
+    ev = [vec(E) for _ in range(4)]
+    wv = [vec(8) for _ in range(4)]
+    mirror, dh_o, dx_o, order = vec(E, i32), torch.empty((5, 8)), torch.empty((5, 3)), vec(5, i32)
+    for deal, name in ((None, "fabind_inter_attn_bwd"), ((order, 1, 3), "fabind_inter_attn_bwd_rows")):
+        r = K.inter_attn_bwd(qkv, cv, 8, d, ev[0], rowptr, col, mirror, ridx, wv[0], wv[1], wv[2], wv[3], ev[1], ev[2], 0.5, dh_o, dx_o, 2, deal)
+        a = fk.last(name)
+        assert a[:21] == [A(qkv), 28, A(cv), 12, 8, A(d), A(ev[0]), A(rowptr), A(col), A(mirror), A(ridx), A(wv[0]), A(wv[1]), A(wv[2]), A(wv[3]),
+                          A(ev[1]), A(ev[2]), 0.5, 5, A(dh_o), A(dx_o)]
+        assert [tuple(fk.tensor(p).shape) for p in a[21:29]] == [(5, 24), (5, 8), (E, 3), (E,), (E // 2,), (E,), (E,), (2, 32)] and a[29] == 2
+        assert a[30:] == ([ST] if deal is None else [A(order), 1, 3, ST])
+        assert [tuple(x_.shape) for x_ in r] == [(5, 24), (5, 8), (E, 3), (E,), (E // 2,), (E,), (32,)]
+        assert fk.calls[-1][0] == "fabind_colsum" and fk.calls[-1][1][0] == a[28]                 # the four vector gradients: one column sum
+
+    # ---- pair bias adjoint ----
+    lay = NS(B=B, sumP=4, sumC=3, max_P=3, max_C=2, desc_p=desc_p, desc_pf=torch.empty((B, 8), dtype=i32), c_index=vec(3, i32), p_index=vec(4, i32))
+    a0b0, douts, wc = torch.empty((5, 16)), [torch.empty((6, 8)), None], torch.empty((2, 8, 8))
+    Acat, BTcat, colpart = K.pair_bias_cat(douts, lay, 8, 32, a0b0[:, 8:], wc)
+    a = fk.last("fabind_pair_bias_cat")
+    assert a == [[A(douts[0]), None], 2, A(desc_p), B, 3, 32, A(Acat), 64, A(a0b0[:, 8:]), 16, A(lay.c_index), A(wc), 8, A(BTcat), 64, A(colpart), ST]
+    assert Acat.shape == (4, 64) and BTcat.shape == (B * 8, 64) and colpart.shape == (3, 16) and Acat.dtype == BTcat.dtype == bf
+    BT2 = K.pair_bias_btcat(a0b0[:, 8:], lay, wc, 8, 32)
+    assert fk.last("fabind_pair_bias_btcat") == [A(a0b0[:, 8:]), 16, A(lay.c_index), A(desc_p), A(wc), 2, 8, 32, A(BT2), 64, B, ST] and BT2.shape == (B * 8, 64)
+    Dt = K.batched_transpose_pad(Acat, desc_p, B, 2, 32, 64)
+    assert fk.last("fabind_batched_transpose_pad") == [A(Acat), 64, A(desc_p), B, 2, 32, 64, A(Dt), ST] and Dt.shape == (2, B * 32, 64)
+    a16 = v(5, 8, 16, bf)
+    At = K.batched_transpose_pad(a16, lay.desc_pf, B, 1, 8, 64)
+    assert fk.last("fabind_batched_transpose_pad") == [A(a16), 16, A(lay.desc_pf), B, 1, 8, 64, A(At), ST] and At[0].shape == (B * 8, 64)
+    assert K.pair_bias_finish_parts(3) == 2 and K.cross_attn_fused_bwd_parts(B, 3) == 3
+    Tm, da, fin = torch.empty((24, 8)), torch.empty((5, 16)), torch.empty((2, 128))
+    K.pair_bias_finish(Tm, a0b0, 8, wc[1], lay.c_index, 3, da, fin[:, 64:])
+    assert fk.last("fabind_pair_bias_finish") == [A(Tm), A(a0b0), 16, 8, A(wc[1]), A(lay.c_index), 3, A(da), A(fin[:, 64:]), 128, ST]
+    dwk = K.pair_bias_bwd(douts[0], 8, a0b0, 8, wc[0], lay, da)
+    assert fk.last("fabind_pair_bias_bwd") == [A(douts[0]), 8, A(a0b0), 16, 8, A(wc[0]), A(desc_p), B, 3, 2, A(lay.p_index), A(lay.c_index), A(da),
+                                               A(dwk), ST] and dwk.shape == (B, 64)
+    # the shared tail of ops: launch order and the operands of every launch, for a block list with a gap
+    n0 = len(fk.calls)
+    monkeypatch.setattr(ops, "_pair_bias_groups", lambda *a_: (vec(8, i32), vec(8, i32)))
+    lay.n_pairs = 6
+    dw = ops._pair_bias_adjoint_tail(lay, 8, a0b0, a16, da, Acat, BTcat, wc, [1], 32)
+    assert [n_ for n_, _ in fk.calls[n0:]] == ["fabind_gemm", "fabind_batched_transpose_pad", "fabind_batched_transpose_pad", "fabind_gemm",
+                                               "fabind_pair_bias_finish", "fabind_colsum"] and dw.shape == (2, 8, 8)
+    g0, g1 = fk.calls[n0][1][0], fk.calls[n0 + 3][1][0]
+    assert (g0["A"], g0["W"], g0["C"], g0["accumulate"], g0["ldc"], g0["M"], g0["N"], g0["n_groups"], g0["max_m"], g0["max_n"]) == \
+        (A(Acat), A(BTcat), A(da), 1, 16, 4, B * 8, B, 3, 8)
+    assert (g1["lda"], g1["ldw"], g1["ldc"], g1["M"], g1["N"], g1["K"], g1["max_m"], g1["accumulate"]) == (64, 64, 8, B * 32, B * 8, 64, 16, 0)
+    fi = fk.calls[n0 + 4][1]
+    assert fi[1:4] == [A(a0b0), 16, 8] and fi[4] == A(wc[1]) and fi[7] == A(da) and fi[9] == 128 and fk.tensor(fi[8]).shape == (2, 64)
+
+    # ---- norms and heads ----
+    xc, w8, b8 = torch.empty((5, 8)), vec(8), vec(8)
+    y, mean, rstd = K.layernorm_fwd(xc, w8, b8, 1e-5)
+    assert fk.last("fabind_layernorm_fwd") == [A(xc), A(w8), A(b8), 1e-5, 5, 8, A(y), A(mean), A(rstd), ST]
+    dxl, dwl, dbl = K.layernorm_bwd(xc, w8, y, mean, rstd)
+    a = fk.last("fabind_layernorm_bwd")
+    assert a[:8] == [A(xc), A(w8), A(y), A(mean), A(rstd), 5, 8, A(dxl)] and fk.tensor(a[8]).shape == fk.tensor(a[9]).shape == (2, 8) and dwl.shape == (8,)
+    x6, w6, dy6 = v(5, 6, 12, bf), vec(6), v(5, 6, 16)
+    dx6, dw6, db6 = K.layernorm_rows_bwd(x6, w6, dy6)
+    a = fk.last("fabind_layernorm_rows_bwd")
+    assert a[:13] == [A(x6), 1, 12, A(w6), A(dy6), 0, 16, 1e-5, 5, 6, A(dx6), 1, 8] and a[15:] == [2, ST] and dx6.shape == (5, 6) and dw6.shape == (6,)
+    y = K.edge_concat(x, row, col, rho, bf, 24)
+    assert fk.last("fabind_edge_concat") == [A(x), 12, 8, A(row), A(col), A(rho), E, A(y), 1, 24, 24, ST] and y.shape == (E, 24)
+    lg, m8, xyz, noise = torch.empty((B, 5)), torch.empty((B, 5), dtype=torch.uint8), torch.empty((B, 5, 3)), torch.empty((B, 5, 2))
+    center, wsum = K.pocket_center_fwd(lg, m8, xyz, noise, 0.5, True)
+    assert fk.last("fabind_pocket_center_fwd") == [A(lg), A(m8), A(xyz), A(noise), B, 5, 0.5, 1, A(center), A(wsum), ST]
+    dc = torch.empty((B, 3))
+    dlg = K.pocket_center_bwd(lg, m8, xyz, None, 0.5, center, wsum, dc)
+    assert fk.last("fabind_pocket_center_bwd") == [A(lg), A(m8), A(xyz), None, B, 5, 0.5, A(center), A(wsum), A(dc), A(dlg), ST]
+    co, ct, yp, yb, dm, cls, cen, cent = torch.empty((4, 3)), torch.empty((4, 3)), vec(6), vec(6), vec(6), torch.empty((B, 5)), torch.empty((B, 3)), torch.empty((B, 3))
+    w = dict(coord=1.0, pair=2.0, distill=3.0, cls=4.0, center=5.0, delta=6.0)
+    loss, terms, lo8 = K.loss_fwd(co, ct, yp, yb, dm, lg, cls, 0, m8, cen, cent, w)
+    a = fk.last("fabind_loss_fwd")
+    assert a[:21] == [A(co), A(ct), 12, A(yp), A(yb), A(dm), 6, A(lg), A(cls), 0, A(m8), 10, A(cen), A(cent), 6, 1.0, 2.0, 3.0, 4.0, 5.0, 6.0]
+    assert fk.tensor(a[21]).shape == (2, 8) and fk.tensor(a[22]) is list(K.LOSS_TICKET.values())[0] and a[23:] == [A(lo8), A(loss), A(terms), ST]
+    gl, gt, dl = torch.empty(()), vec(6), [torch.empty_like(co), None, torch.empty_like(yb), None, torch.empty_like(cen)]
+    K.loss_bwd(co, ct, yp, yb, dm, lg, cls, 0, cen, cent, w, lo8, gl, gt, dl)
+    assert fk.last("fabind_loss_bwd") == [A(co), A(ct), 12, A(yp), A(yb), A(dm), 6, A(lg), A(cls), 0, 10, A(cen), A(cent), 6, 1.0, 2.0, 3.0, 4.0, 5.0, 6.0,
+                                          A(lo8), A(gl), A(gt), A(dl[0]), None, A(dl[2]), None, A(dl[4]), ST]
+    bl2 = NS(desc_ptr=A(raw), B=B, n_tiles=3, n_pairs=6, max_C=2)
+    xp, xl = torch.empty((4, 3)), torch.empty((3, 3))
+    yd = K.pair_dist_fwd(bl2, xp, xl, 5.0, 0.0, 10.0)
+    assert fk.last("fabind_pair_dist_fwd") == [A(raw), B, 3, A(xp), A(xl), 5.0, 0.0, 10.0, A(yd), ST] and yd.shape == (6,)
+    dxl = K.pair_dist_bwd(bl2, xp, xl, yd, 5.0, 0.0, 10.0)
+    a = fk.last("fabind_pair_dist_bwd")
+    assert a[:9] == [A(raw), B, 2, A(xp), A(xl), A(yd), 5.0, 0.0, 10.0] and fk.tensor(a[9]).shape == (B, 8, 2, 3) and a[10:] == [A(dxl), ST]
+    rmsd, cdis = K.pose_stats(co, ct, lo, B)
+    assert fk.last("fabind_pose_stats") == [A(co), A(ct), A(lo), B, A(rmsd), A(cdis), ST] and rmsd.shape == cdis.shape == (B,)
+    sc, rm, goff = vec(6), vec(6), vec(3, i32)
+    terms, dsc, counts = K.rank_loss_fwd(sc, rm, goff, 2, 1, True)
+    assert fk.last("fabind_rank_loss_fwd") == [A(sc), A(rm), A(goff), 2, 1, 1, A(terms), A(dsc), A(counts), ST] and terms.shape == (2, 3) and counts.dtype == i32
+    # every entry point that ops.py, engine.py and plus/engine.py reach through the wrappers above was driven
+    moved = {"fabind_transpose_act", "fabind_mul_dact", "fabind_mul_dact_colsum", "fabind_mul_dropmask_colsum", "fabind_gemm", "fabind_rowdot_bwd",
+             "fabind_edge_geom_bwd", "fabind_gcl_pre_bwd", "fabind_gather_dact", "fabind_coord_update_bwd", "fabind_drop_mix", "fabind_drop_mix_bwd",
+             "fabind_cross_attn_bwd", "fabind_cross_attn_mfma_bwd", "fabind_pair_hadamard", "fabind_pair_hadamard_bwd", "fabind_pair_hadamard_bwd_rows",
+             "fabind_pair_hadamard_bwd_grid", "fabind_rows_hadamard_bwd", "fabind_block_hadamard_fwd", "fabind_block_hadamard_bwd",
+             "fabind_inter_attn_bwd", "fabind_inter_attn_bwd_rows", "fabind_las_step_bwd", "fabind_pair_bias_cat", "fabind_pair_bias_btcat",
+             "fabind_batched_transpose_pad", "fabind_pair_bias_finish", "fabind_pair_bias_bwd", "fabind_layernorm_fwd", "fabind_layernorm_bwd",
+             "fabind_layernorm_rows_bwd", "fabind_edge_concat", "fabind_pocket_center_fwd", "fabind_pocket_center_bwd", "fabind_loss_fwd",
+             "fabind_loss_bwd", "fabind_pair_dist_fwd", "fabind_pair_dist_bwd", "fabind_lower_bound", "fabind_pose_stats", "fabind_rank_loss_fwd",
+             "fabind_colsum"}
+    assert moved <= {n_ for n_, _ in fk.calls}

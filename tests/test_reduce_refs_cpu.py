@@ -132,7 +132,6 @@ def test_launch_constants_match_the_sources():
     gcl = open(os.path.join(ROOT, "fabind_amd", "csrc", "gcl.hip")).read()
     bwd = open(os.path.join(ROOT, "fabind_amd", "csrc", "bwd.hip")).read()
     gemm = open(os.path.join(ROOT, "fabind_amd", "csrc", "gemm.hip")).read()
-    ops = open(os.path.join(ROOT, "fabind_amd", "ops.py")).read()
     kern = open(os.path.join(ROOT, "fabind_amd", "kernels.py")).read()
     for text, src in (("const int heavy_min = n_rows < 16384 ? 32 : 128;", gcl),
                       ("while (rpw > 64 && (n_rows + rpw - 1) / rpw < 256) rpw >>= 1;", gcl),
@@ -141,8 +140,8 @@ def test_launch_constants_match_the_sources():
                       ("if (e1 - e0 > heavy_min) return;", gcl), ("rowptr[rr + 1] - rowptr[rr] > heavy_min", gcl),
                       ("for (; r + 12 < r1; r += 16)", bwd), ("for (; k + 48 < nchunk; k += 64)", bwd), ("const int t = c / 128;", bwd),
                       ("for (; r + 12 < r1; r += 16)", gemm), ("for (int k = q; k < nchunk; k += 4)", gemm),
-                      ("nchunk = max(1, min(4096, (R + 63) // 64))", ops), ("nchunk = max(1, min(2048, (E + 255) // 256))", ops),
-                      ("return max(1, min(1024, (rows + 255) // 256))", ops), ("nchunk = max(1, min(1024, (R + 255) // 256))", kern)):
+                      ("return max(1, min(4096, (rows + 63) // 64))", kern), ("nchunk = max(1, min(2048, (E + 255) // 256))", kern),
+                      ("return max(1, min(1024, (rows + 255) // 256))", kern)):
         assert text in src, text
 
 

@@ -60,6 +60,8 @@ def pack_samples(samples, pin=True):
     """Host side: flatten a list of raw complexes into (float32 buffer, int64 buffer, layout).  Each sample is a mapping
     with `protein_node_xyz [L,3]`, `protein_esm2_feat [L,Fp]`, `coords [Nc,3]` (native ligand), `compound_node_features
     [Nc,Fc]`, `rdkit_coords [Nc,3]`, `input_atom_edge_list [Eb,>=2]`, `LAS_edge_index [2,El]` (array-likes), `pdb`.
+    `LAS_edge_index` may be given for every sample of a batch or for none: without it `build_batch` derives the pairs on the device
+    from `input_atom_edge_list` (fabind_amd/topology.py).
     Optional, in all samples or in none: `bond_codes [Eb]` aligned with `input_atom_edge_list` (`symmetry.bond_code` coding; what
     `build_batch(torsion_noise=True)` needs) and `augment_key` (an int naming the complex for the augmentation's random draws)."""
     a = lambda v, dt: np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v, dtype=dt)
@@ -69,7 +71,13 @@ def pack_samples(samples, pin=True):
         lay[f] = (sum(p.size for p in floats), [p.shape for p in parts])
         floats.extend(p.reshape(-1) for p in parts)
     bonds = [a(s["input_atom_edge_list"], np.int64)[:, :2] for s in samples]
-    las = [a(s["LAS_edge_index"], np.int64).T for s in samples]
+    if any("LAS_edge_index" in s for s in samples):
+        if not all("LAS_edge_index" in s for s in samples):
+            raise ValueError("fabind_amd.data: the field LAS_edge_index must be given for every sample of a batch or for none")
+        las = [a(s["LAS_edge_index"], np.int64).T for s in samples]
+    else:
+        las = [np.zeros((0, 2), np.int64) for _ in samples]
+        lay["derive_las"] = True
     counts = np.array([[s_["protein_node_xyz"].shape[0], s_["coords"].shape[0], b.shape[0], l.shape[0]]
                        for s_, b, l in zip(samples, bonds, las)], dtype=np.int64)
     tail = []
@@ -100,7 +108,7 @@ def pack_samples(samples, pin=True):
 @torch.no_grad()
 def build_batch(samples, device, pocket_radius=20.0, interaction_threshold=10.0, add_noise_to_com=None,
                 pocket_idx_no_noise=True, generator=None, packed=None, random_rotation=False, torsion_noise=False, augment_seed=0,
-                augment_keys=None):
+                augment_keys=None, las_on_overflow="raise"):
     """-> HeteroBatch on `device` with every field of SURVEY.md A.10 (what `IaBNet.forward / inference`, the losses and the
     evaluation loop read).  `add_noise_to_com`: uniform +-noise on the crop centre (the reference's train-time option,
     utils/utils.py:129-130), drawn from `generator`.
@@ -108,7 +116,9 @@ def build_batch(samples, device, pocket_radius=20.0, interaction_threshold=10.0,
     formed (the reference's train group, utils/utils.py:307-311).  `torsion_noise` (FABind+ --train-ligand-torsion-noise,
     :285-304): the start conformer is made from the NATIVE ligand `coords` instead -- every rotatable bond set to a uniform random
     dihedral, centred, rotated; needs the sample field `bond_codes`.  Draws are keyed by (`augment_seed`, key of the complex):
-    `augment_keys` [B], else the samples' `augment_key`, else the position in the batch.  Both off: the code path without them."""
+    `augment_keys` [B], else the samples' `augment_key`, else the position in the batch.  Both off: the code path without them.
+    Samples packed without `LAS_edge_index`: the LAS pairs come from `topology.las_pairs` on the bond list (one more read-back, on the
+    current stream); `las_on_overflow` is its `on_overflow`."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("fabind_amd.data.build_batch assembles batches on a HIP device; got %s" % dev)
@@ -138,6 +148,8 @@ def build_batch(samples, device, pocket_radius=20.0, interaction_threshold=10.0,
     cb = torch.repeat_interleave(ar(B), Nc)
     bb = torch.repeat_interleave(ar(B), Eb)
     lb = torch.repeat_interleave(ar(B), El)
+    if lay.get("derive_las"):
+        las, lb = _derive_las(bonds, Nc, bb, B, lig.shape[0], las_on_overflow)
     # ---- centre on the protein, crop the pocket around the ligand centroid (utils/utils.py:208-229, 121-144)
     bias = _seg_mean(prot, pb, B)
     prot, lig = prot - bias[pb], lig - bias[cb]
@@ -206,6 +218,17 @@ def build_batch(samples, device, pocket_radius=20.0, interaction_threshold=10.0,
     data.pocket_residue_center = pocket_centre                 # FABind+ (model.py:176-183)
     data.pdb = lay["pdb"]
     return data
+
+
+def _derive_las(bonds, Nc, bb, B, n_atoms, on_overflow):
+    """(las int64 [El, 2] LOCAL atom ids, lb [El] the complex of every pair) from the bond lists (fabind_amd/topology.py)."""
+    from . import topology
+    aoff = _offsets(Nc)
+    p = topology._pairs((bonds + aoff[bb][:, None]).t().contiguous(), aoff.to(torch.int32), n_atoms, on_overflow,
+                        "fabind_amd.data.build_batch")
+    lb = torch.repeat_interleave(torch.arange(B, device=bonds.device), (p.off[1:] - p.off[:-1]).to(torch.long),
+                                 output_size=p.edge_index.shape[1])
+    return (p.edge_index - aoff[lb][None, :]).t().contiguous(), lb
 
 
 def _augment(lig, rdk, bonds, idv, lay, Nc, bb, nb, nl, torsion_noise, seed, keys):

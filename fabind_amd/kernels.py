@@ -445,6 +445,14 @@ def las_step(x, x0, las_i, las_j, las_off, node_off, c_cnt, B, max_n, step, clam
     return (x_out, mask) if want_mask else x_out
 
 
+def las_pairs(nbr_ptr, nbr_idx, atom_off, n_ligands, row_count, mask_rows, ring_pairs, status, row_off=None, n_pairs=0, edge_index=None):
+    """csrc/topology.hip.  edge_index=None: the count pass (row_count, mask_rows, ring_pairs, status are written); else the write pass
+    into edge_index int64 [2, n_pairs] at the offsets row_off."""
+    check(_lib.load().fabind_las_pairs(ptr(nbr_ptr), ptr(nbr_idx), ptr(atom_off), int(n_ligands), int(nbr_idx.numel()), ptr(row_count),
+                                       ptr(mask_rows), ptr(ring_pairs), ptr(status), ptr(row_off), int(n_pairs), ptr(edge_index), stream()),
+          "fabind_las_pairs(%s)" % ("count" if edge_index is None else "write"))
+
+
 def select_rows(x, z, mask_u8):
     out = torch.empty_like(x)
     check(_lib.load().fabind_select_rows(ptr(x), ptr(z), ptr(mask_u8), x.shape[0], x.shape[1], ptr(out), stream()),

@@ -78,6 +78,7 @@ const char* fabind_last_error(void);
  *     Likewise the form report of csrc/norm.hip (fabind_layernorm_rows_form, _rows_bwd_form, fabind_row_stats_form, fabind_edge_lnfold_form /
  *     _blocks, fabind_edge_lnfold_bwd_form, fabind_inter_coord_fold_blocks + FB_LNR_* / FB_LNB_* / FB_RST_* / FB_ELF_* / FB_ELB_*).
  *     Likewise fabind_torsion_plan / fabind_conformer_perturb (csrc/conformer.hip: train-time torsion noise and random rotation).
+ *     Likewise fabind_las_pairs (csrc/topology.hip: LAS constraint pairs from the bond list).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -519,6 +520,21 @@ int fabind_torsion_plan(const int* nbr_ptr, const int* nbr_idx, const int* nbr_c
 int fabind_conformer_perturb(const float* x, const int* atom_off, int n_ligands, int n_atoms, int n_copies, const int* tor_off,
                              const int* quad, const unsigned* side, const float* angles, int t_total, const float* uniforms,
                              const int* keys, unsigned seed, int relative, int rotate, int centre, float* out, hipStream_t stream);
+/* LAS ("local atomic structure") constraint pairs of a BATCH of ligands from their bond lists (FABind/fabind/utils/generation_utils.py:
+ * 170-187 get_LAS_distance_constraint_mask).  nbr_ptr int32 [sum atoms + 1] / nbr_idx int32 [n_entries] (GLOBAL atom ids): the
+ * symmetrised, de-duplicated neighbour lists without self-loops, sorted by owner and then by neighbour; atom_off int32 [n_ligands + 1].
+ * Pair (i, j), i != j, of one ligand is kept iff i and j are bonded, have a common neighbour, or lie on a common relevant cycle (a
+ * cycle whose edge set is no GF(2) sum of strictly shorter cycles).
+ *   Count mode (edge_index = NULL): row_count int32 [sum atoms] = pairs of every atom's row; mask_rows uint32 [sum atoms, 8] = the
+ *   256-bit row of every atom of a ligand of at most 256 atoms (bit j of word j / 32); ring_pairs int32 [n_ligands] = unordered pairs
+ *   on a common relevant cycle; status int32 [n_ligands] = 0, 3 (more than 256 atoms) or 4 (more than 64 non-tree bonds): such a ligand
+ *   gets the bonded and common-neighbour pairs only.
+ *   Write mode (the same mask_rows; row_off int32 [sum atoms + 1] = exclusive sums of row_count, n_pairs = row_off[sum atoms]):
+ *   edge_index int64 [2, n_pairs], GLOBAL atom ids, row i's pairs at [row_off[i], row_off[i + 1]) in ascending j -- ligand by ligand,
+ *   row-major: the order of dense_to_sparse.  Nothing is written at or beyond n_pairs.  Integer arithmetic only, no atomics. */
+int fabind_las_pairs(const int* nbr_ptr, const int* nbr_idx, const int* atom_off, int n_ligands, int n_entries, int* row_count,
+                     unsigned* mask_rows, int* ring_pairs, int* status, const int* row_off, long n_pairs, long long* edge_index,
+                     hipStream_t stream);
 /* FABind+ confidence training (FABind_plus/fabind/utils/training_confidence.py:41-77, :215-252).
  * fabind_pose_stats: per sample b over the atoms [atom_off[b], atom_off[b + 1]) (atom_off int32 [B + 1]; pred / truth fp32 [n_atoms, 3]):
  *   rmsd[b] = sqrt(mean_i |p_i - t_i|^2), cdis[b] = |mean_i (p_i - t_i)| (the distance of the two centroids); an empty sample gives

@@ -125,6 +125,8 @@ SIGNATURES = {
     "fabind_las_pairs": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp],
     "fabind_pose_stats": [_vp, _vp, _vp, _i, _vp, _vp, _vp],
     "fabind_rank_loss_fwd": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "fabind_pose_pair_rmsd": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "fabind_pose_cluster": [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
     "fabind_multi_copy": [_vp, _i, _i, _vp],
     "fabind_adam_chunk": [],
     "fabind_multi_sqnorm": [_vp, _i, _i, _vp, _vp, _vp, _vp],

@@ -1557,3 +1557,24 @@ def rank_loss_fwd(scores, rmsd, group_off, G, mode, with_ce):
     check(_lib.load().fabind_rank_loss_fwd(ptr(scores), ptr(rmsd), ptr(group_off), G, mode, int(with_ce), ptr(terms), ptr(d_scores),
                                            ptr(counts), stream()), "fabind_rank_loss_fwd")
     return terms, d_scores, counts
+
+
+def pose_pair_rmsd(poses, aoff, flat_off, use_cnt, flat, B, max_atoms):
+    """D [B, S, S] of csrc/pose_cluster.hip: the (symmetry-corrected) RMSD of every pair of the fp32 [S, N, 3] poses of each ligand."""
+    S, N = poses.shape[0], poses.shape[1]
+    D = torch.empty((B, S, S), dtype=torch.float32, device=poses.device)
+    check(_lib.load().fabind_pose_pair_rmsd(ptr(poses), S, N, ptr(aoff), ptr(flat_off), ptr(use_cnt), ptr(flat), B, max_atoms, ptr(D),
+                                            stream()), "fabind_pose_pair_rmsd")
+    return D
+
+
+def pose_cluster(D, conf, threshold):
+    """Leader clustering (csrc/pose_cluster.hip) of D fp32 [B, S, S] under conf fp32 [S, B] -> int32 cluster_id, leader, size [S, B]
+    and n_clusters [B]."""
+    B, S = D.shape[0], D.shape[1]
+    cid = torch.empty((S, B), dtype=torch.int32, device=D.device)
+    leader, size = torch.empty_like(cid), torch.empty_like(cid)
+    ncl = torch.empty(B, dtype=torch.int32, device=D.device)
+    check(_lib.load().fabind_pose_cluster(ptr(D), ptr(conf), S, B, float(threshold), ptr(cid), ptr(leader), ptr(size), ptr(ncl), stream()),
+          "fabind_pose_cluster")
+    return cid, leader, size, ncl

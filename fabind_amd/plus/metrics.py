@@ -7,7 +7,11 @@ losses back per batch; here the ranking kernel (csrc/ranking.hip) returns the fo
 device, and `compute()` reads everything back in one transfer.
 
 `select_by_confidence` / `sampling_metrics` are the top-N evaluation of test_sampling_fabind.py:159-191 (FABind+'s sampling table)
-on [S, B] tensors instead of S text files; they run once per evaluation and are plain torch."""
+on [S, B] tensors instead of S text files; they run once per evaluation and are plain torch.
+
+`select_distinct_by_confidence` / `distinct_sampling_metrics` are the same evaluation over DISTINCT poses: the leaders of the first
+`top_n` clusters of `fabind_amd.poses.cluster_poses` instead of the `top_n` most confident samples, which are usually one binding mode
+several times."""
 import torch
 
 from .models.model import confidence_terms
@@ -94,4 +98,35 @@ def sampling_metrics(rmsd, cdis, conf, top_n=1):
     for x, p in ((r.double(), "rmsd"), (c.double(), "centroid_dis")):
         names += [p + s for s in ("_mean", "_2A", "_5A", "_25", "_50", "_75")]
         vals += [x.mean(), (x < 2).double().mean(), (x < 5).double().mean()] + [torch.quantile(x, q) for q in (0.25, 0.50, 0.75)]
+    return dict(zip(names, torch.stack(vals).tolist()))
+
+
+def select_distinct_by_confidence(rmsd, cdis, conf, clusters, top_n=1):
+    """`select_by_confidence` over distinct poses: per complex the minimum RMSD and the minimum centroid distance among the leaders of
+    its first `top_n` clusters (`clusters`: the `poses.PoseClusters` of the same [S, B] samples, clusters in the confidence order of
+    their leaders).  A complex with fewer than `top_n` clusters uses the clusters it has.
+    -> (rmsd [B], centroid distance [B], the chosen pose indices int64 [top_n, B], -1 where a complex has no such cluster)."""
+    if rmsd.dim() != 2 or tuple(cdis.shape) != tuple(rmsd.shape) or tuple(conf.shape) != tuple(rmsd.shape) or \
+            tuple(clusters.leader.shape) != tuple(rmsd.shape):
+        raise ValueError("select_distinct_by_confidence: rmsd, cdis, conf and clusters.leader must share one [S, B] shape; got %s, %s, %s, %s"
+                         % (tuple(rmsd.shape), tuple(cdis.shape), tuple(conf.shape), tuple(clusters.leader.shape)))
+    if not 1 <= int(top_n) <= rmsd.shape[0]:
+        raise ValueError("select_distinct_by_confidence: top_n must be in [1, S = %d]; got %r" % (rmsd.shape[0], top_n))
+    pick = clusters.leader[:int(top_n)].long()
+    have, at = pick >= 0, pick.clamp(min=0)
+    inf = torch.full_like(rmsd[:1], float("inf"))
+    return (torch.where(have, rmsd.gather(0, at), inf).min(0).values, torch.where(have, cdis.gather(0, at), inf).min(0).values, pick)
+
+
+def distinct_sampling_metrics(rmsd, cdis, conf, clusters, top_n=1):
+    """The dictionary of `sampling_metrics` on `select_distinct_by_confidence`, plus `n_clusters_mean` (clusters per complex) and
+    `top_cluster_share` (the mean over complexes of the population of cluster 0 over S: how much of the sampling agrees with the most
+    confident pose).  -> dict of python floats, one read-back."""
+    r, c, _ = select_distinct_by_confidence(rmsd, cdis, conf, clusters, top_n)
+    vals, names = [], []
+    for x, p in ((r.double(), "rmsd"), (c.double(), "centroid_dis")):
+        names += [p + s for s in ("_mean", "_2A", "_5A", "_25", "_50", "_75")]
+        vals += [x.mean(), (x < 2).double().mean(), (x < 5).double().mean()] + [torch.quantile(x, q) for q in (0.25, 0.50, 0.75)]
+    names += ["n_clusters_mean", "top_cluster_share"]
+    vals += [clusters.n_clusters.double().mean(), clusters.size[0].double().mean() / rmsd.shape[0]]
     return dict(zip(names, torch.stack(vals).tolist()))

@@ -75,6 +75,7 @@ const char* fabind_last_error(void);
  *     point or struct changed, so the version stays.  Likewise fabind_gemm_plan + FB_GEMM_FAM_* (which kernel and epilogue fabind_gemm
  *     selects, reported without a launch).
  *     Likewise fabind_pose_stats / fabind_rank_loss_fwd (csrc/ranking.hip: FABind+ confidence training).
+ *     Likewise fabind_pose_pair_rmsd / fabind_pose_cluster (csrc/pose_cluster.hip: the poses of a complex against each other, leader clustering).
  *     Likewise the form report of csrc/norm.hip (fabind_layernorm_rows_form, _rows_bwd_form, fabind_row_stats_form, fabind_edge_lnfold_form /
  *     _blocks, fabind_edge_lnfold_bwd_form, fabind_inter_coord_fold_blocks + FB_LNR_* / FB_LNB_* / FB_RST_* / FB_ELF_* / FB_ELB_*).
  *     Likewise fabind_torsion_plan / fabind_conformer_perturb (csrc/conformer.hip: train-time torsion noise and random rotation).
@@ -553,6 +554,24 @@ int fabind_las_pairs(const int* nbr_ptr, const int* nbr_idx, const int* atom_off
 int fabind_pose_stats(const float* pred, const float* truth, const int* atom_off, int B, float* rmsd, float* cdis, hipStream_t stream);
 int fabind_rank_loss_fwd(const float* scores, const float* rmsd, const int* group_off, int G, int mode, int with_ce, float* terms,
                          float* d_scores, int* counts, hipStream_t stream);
+/* The sampled poses of every complex against each other (csrc/pose_cluster.hip).  Backward-compatible additions under ABI 19.
+ * fabind_pose_pair_rmsd: D fp32 [n_ligands, n_pose, n_pose],
+ *   D[b, s, t] = min over the automorphisms a of ligand b of sqrt((1 / n_b) sum_i |x_s[off_b + a[i]] - x_t[off_b + i]|^2)
+ *   (no centring, no superposition: the definition of fabind_sym_score) for poses fp32 [n_pose, n_atoms, 3]; atom_off, flat_off,
+ *   auto_cnt, flat as fabind_sym_score takes them (auto_cnt[b] = 0: the identity alone, plain RMSD; never more entries than the
+ *   ligand's slot of flat holds; an entry outside [0, n_b) counts as i).  Every unordered pair is computed once and written to both
+ *   triangles (D is exactly symmetric), the diagonal is +0.0, a ligand without atoms gets 0.  The sum of a pair is formed in an order
+ *   fixed by the ligand alone and minima are taken on bit patterns: D[b, s, t] is the same bits in any batch and among any n_pose
+ *   poses.  No float atomics.  n_pose <= 512 and max_atoms (>= every n_b) <= 2048, refused otherwise before anything is launched.
+ * fabind_pose_cluster: leader clustering of every ligand's poses on D with conf fp32 [n_pose, n_ligands]: rank by descending confidence
+ *   (equal values in pose order, NaN last); the best unassigned pose leads the next cluster, every unassigned t with
+ *   D[b, leader, t] < threshold (strict; a NaN distance never joins) joins it.  int32 outputs: cluster_id [n_pose, n_ligands] (0 = the
+ *   cluster of the most confident pose); leader / size [n_pose, n_ligands]: row k = cluster k's leading pose and population, -1 / 0
+ *   from row n_clusters[b] on; n_clusters [n_ligands].  One wave per ligand, comparisons and integers only.  n_pose <= 512. */
+int fabind_pose_pair_rmsd(const float* poses, int n_pose, int n_atoms, const int* atom_off, const int* flat_off, const int* auto_cnt,
+                          const int* flat, int n_ligands, int max_atoms, float* D, hipStream_t stream);
+int fabind_pose_cluster(const float* D, const float* conf, int n_pose, int n_ligands, float threshold, int* cluster_id, int* leader,
+                        int* size, int* n_clusters, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross attention (RowAttentionBlock / Attention._attention, models/cross_att.py:118-134,

@@ -122,6 +122,7 @@ SIGNATURES = {
     "fabind_sym_score": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_torsion_plan": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_conformer_perturb": [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, ctypes.c_uint, _i, _i, _i, _vp, _vp],
+    "fabind_conformer_fit": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_las_pairs": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp],
     "fabind_pose_stats": [_vp, _vp, _vp, _i, _vp, _vp, _vp],
     "fabind_rank_loss_fwd": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],

@@ -13,7 +13,11 @@ with RDKit.  Here both run for a whole batch in csrc/conformer.hip:
   ligand's result depends on its key and the seed, never on the batch around it.
 
 RDKit's choice of reference atoms (i, l) and of the moving side is not reproduced: under a uniform target dihedral and a uniform
-rotation of the whole ligand neither changes the distribution of the result."""
+rotation of the whole ligand neither changes the distribution of the result.
+
+* `fit_conformers` (csrc/conformer_fit.hip) is the inverse of `perturb_conformers`: the dihedral changes and the rigid motion that bring
+  the start conformer closest to a target pose, atom by atom -- a predicted coordinate cloud turned into a molecule with the start
+  conformer's bond lengths, angles and rings.  One wave per (ligand, pose), all iterations in one launch."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -24,7 +28,9 @@ from ._lib import check, ptr, stream
 from .symmetry import _atom_off, bond_code
 
 MAX_ATOMS = 256
-STATUS = {0: "ok", 3: "more than 256 atoms"}
+MAX_FIT_TORSIONS = 58
+STATUS = {0: "ok", 3: "more than 256 atoms", 4: "more than 58 torsions"}
+STOP = {0: "converged", 1: "iteration cap", 2: "rejections"}
 
 
 @dataclass
@@ -190,6 +196,108 @@ def perturb_conformers(coords, plan=None, n_copies=1, seed=0, keys=None, torsion
                                                ptr(uni), ptr(k), int(seed) & 0xFFFFFFFF, int(bool(relative)), int(bool(random_rotation)),
                                                int(bool(centre)), ptr(out), stream()), "fabind_conformer_perturb")
     return out
+
+
+@dataclass
+class ConformerFit:
+    """What `fit_conformers` returns, all on the device.  coords: float32 [S, N, 3], the fitted poses; angles: float32 [S, T] in
+    (-pi, pi], plan order: `perturb_conformers(conformer, plan, angles=angles, relative=True, random_rotation=False, centre=False)`
+    is `coords` up to a rigid motion; rmsd0 / rmsd: float32 [S, B], to the target after the rigid fit alone / at the end; iters:
+    int32 [S, B] accepted steps; stop: int32 [S, B], a key of STOP; status: int32 [B], a key of STATUS (3 / 4: rigid fit only);
+    trace: float64 [S, B, max_iters] E = n rmsd^2 after each accepted step, NaN behind the last -- or None."""
+    coords: torch.Tensor
+    angles: torch.Tensor
+    rmsd0: torch.Tensor
+    rmsd: torch.Tensor
+    iters: torch.Tensor
+    stop: torch.Tensor
+    status: torch.Tensor
+    trace: object = None
+
+
+def fit_conformers(conformer, target, plan=None, max_iters=50, tol=1e-6, return_trace=False, on_overflow="raise", atom_off=None,
+                   compound_batch=None, out=None):
+    """Fit the start conformer of every ligand to target poses over its rotatable-bond dihedrals and one rigid motion.
+
+    conformer: [N, 3] on the HIP device; target: [N, 3] or [S, N, 3], matched atom by atom; plan: the TorsionPlan of the same ligands.
+    Damped Gauss-Newton on sum |pose(a) - target|^2 (csrc/conformer_fit.hip), at most `max_iters` accepted steps, stopped early by an
+    accepted step that lowered the sum by no more than `tol` times itself or by 8 rejected trials in a row.  The defaults rest on a
+    float64 experiment on the host only.
+    plan=None needs `atom_off` [B + 1] or a sorted `compound_batch` [N]: the rigid fit (Horn's quaternion method, a proper rotation
+    always) of every ligand onto every target, angles [S, 0].
+    on_overflow: "raise" -> RuntimeError naming every ligand of more than 256 atoms or more than 58 torsions; "truncate" -> such a
+    ligand gets the rigid fit only (status 3 / 4, zero angles).
+    out: an optional contiguous float32 [S, N, 3] tensor on the device for the coordinates.  -> ConformerFit."""
+    if on_overflow not in ("raise", "truncate"):
+        raise ValueError("on_overflow must be 'raise' or 'truncate'")
+    if not torch.is_tensor(conformer) or not conformer.is_cuda or not torch.is_tensor(target) or not target.is_cuda:
+        raise RuntimeError("fabind_amd: fit_conformers runs on a HIP device only (no CPU fallback)")
+    dev = conformer.device
+    x = conformer.detach().to(torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError("conformer must be [N, 3]; got %s" % (tuple(conformer.shape),))
+    N = x.shape[0]
+    y = target.detach().to(device=dev, dtype=torch.float32)
+    if y.dim() == 2:
+        y = y[None]
+    if y.dim() != 3 or tuple(y.shape[1:]) != (N, 3) or y.shape[0] < 1 or y.shape[0] > 65535:
+        raise ValueError("target must be [%d, 3] or [S, %d, 3] with 1 <= S <= 65535; got %s" % (N, N, tuple(target.shape)))
+    y = y.contiguous()
+    S = y.shape[0]
+    max_iters = int(max_iters)
+    if max_iters < 0 or max_iters > 65536:
+        raise ValueError("max_iters must be in [0, 65536]")
+    tol = float(tol)
+    if not (tol >= 0.0 and tol < 1.0):
+        raise ValueError("tol must be in [0, 1)")
+    if plan is None:
+        if atom_off is None:
+            if compound_batch is None:
+                raise ValueError("without a plan pass atom_off or compound_batch")
+            cb = torch.as_tensor(compound_batch).to(dev).long()
+            atom_off = torch.zeros(int(cb.max()) + 2 if cb.numel() else 1, dtype=torch.int64, device=dev)
+            atom_off[1:] = torch.cumsum(torch.bincount(cb), 0)
+        aoff = _atom_off(atom_off, dev, N)
+    else:
+        aoff = _atom_off(plan.atom_off, dev, N)
+        if atom_off is not None and not torch.equal(aoff, _atom_off(atom_off, dev, N)):
+            raise ValueError("atom_off does not match the ligands of `plan`")
+    B = aoff.numel() - 1
+    ah = aoff.cpu().numpy()
+    counts = np.diff(ah)
+    T, tcount = 0, np.zeros(B, np.int64)
+    if plan is not None:
+        T = int(plan.quad.shape[0])
+        oh = plan.off.cpu().numpy()
+        if (plan.off.dtype != torch.int32 or oh.shape != (B + 1,) or oh[0] != 0 or (np.diff(oh) < 0).any() or int(oh[-1]) != T
+                or tuple(plan.quad.shape) != (T, 4) or tuple(plan.side.shape) != (T, 8) or plan.quad.dtype != torch.int32
+                or plan.side.dtype != torch.int32 or not (plan.quad.is_contiguous() and plan.side.is_contiguous() and plan.off.is_contiguous())
+                or plan.quad.device != dev or plan.side.device != dev or plan.off.device != dev):
+            raise ValueError("inconsistent TorsionPlan")
+        tcount = np.diff(oh)
+    code = np.where(counts > MAX_ATOMS, 3, np.where(tcount > MAX_FIT_TORSIONS, 4, 0))
+    bad = np.nonzero(code)[0]
+    if len(bad) and on_overflow == "raise":
+        raise RuntimeError("fit_conformers: " + "; ".join("ligand %d: status %d (%s)" % (b, code[b], STATUS[int(code[b])]) for b in bad))
+    if out is None:
+        out = torch.empty(S, N, 3, dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.device == dev and out.dtype == torch.float32 and out.is_contiguous()
+              and tuple(out.shape) == (S, N, 3)):
+        raise ValueError("out must be a contiguous float32 [%d, %d, 3] tensor on %s" % (S, N, dev))
+    angles = torch.empty(S, T, dtype=torch.float32, device=dev)
+    rmsd0 = torch.empty(S, B, dtype=torch.float32, device=dev)
+    rmsd = torch.empty(S, B, dtype=torch.float32, device=dev)
+    iters = torch.empty(S, B, dtype=torch.int32, device=dev)
+    stop = torch.empty(S, B, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    trace = torch.empty(S, B, max_iters, dtype=torch.float64, device=dev) if return_trace else None
+    use_plan = plan is not None and T > 0
+    check(_lib.load().fabind_conformer_fit(ptr(x), ptr(y), ptr(aoff), B, N, S, ptr(plan.off) if use_plan else None,
+                                           ptr(plan.quad) if use_plan else None, ptr(plan.side) if use_plan else None, T,
+                                           int(counts.max()) if B else 0, int(tcount.max()) if B else 0, max_iters, tol, ptr(out),
+                                           ptr(angles), ptr(rmsd0), ptr(rmsd), ptr(iters), ptr(stop), ptr(status), ptr(trace), stream()),
+          "fabind_conformer_fit")
+    return ConformerFit(coords=out, angles=angles, rmsd0=rmsd0, rmsd=rmsd, iters=iters, stop=stop, status=status, trace=trace)
 
 
 def _shaped(t, shape, what):

@@ -4,6 +4,7 @@ fabind_inference.py:285-328).
 `post_optimize_compound_coords` keeps the reference's name, arguments and return triple for ONE ligand;
 `post_optimize_compound_coords_batched` runs a whole batch of ligands in one kernel launch (csrc/post_optim.hip: one
 work-group per ligand, all Adam iterations inside the kernel).  HIP device tensors only -- there is no CPU fallback.
+`torsion_fit_compound_coords_batched` has no counterpart in the reference: it moves only what a molecule can move.
 
 Numerics: the objective is non-smooth (|.| and relu) and Adam moves each coordinate by ~lr = 0.1 A per step, so the
 iteration is chaotic: the reference's own result changes by ~0.1 A between its two `torch.cdist` code paths (direct
@@ -59,6 +60,37 @@ def post_optimize_compound_coords_batched(reference_compound_coords, predict_com
                                            0 if LAS_edge_index is not None else 1, int(total_epoch), float(lr), ptr(x),
                                            ptr(loss), ptr(rmsd), stream()), "fabind_post_optimize")
     return x, loss, rmsd
+
+
+def torsion_fit_compound_coords_batched(reference_compound_coords, predict_compound_coords, compound_batch, plan, max_iters=50, tol=1e-6,
+                                        on_overflow="truncate"):
+    """The torsion-space counterpart of `post_optimize_compound_coords_batched`: instead of pulling the predicted cloud towards the
+    start conformer's LAS distances, the start conformer itself is fitted to the prediction over its rotatable-bond dihedrals and
+    one rigid motion (`conformer.fit_conformers`, csrc/conformer_fit.hip), so bond lengths, angles and rings are exactly the start
+    conformer's.  reference / predict: [sum Nc, 3] ([S, sum Nc, 3] for S sampled poses); compound_batch: sorted ligand id per atom;
+    plan: the `conformer.rotatable_bonds` TorsionPlan of the same ligands.  A ligand beyond the kernel's limits (256 atoms, 58
+    torsions) is fitted rigidly (`on_overflow`).
+    -> (x like predict, rmsd_to_prediction [L] ([S, L]), rmsd_rigid [L] ([S, L]): the same after the rigid fit alone)."""
+    from .. import conformer
+    if not predict_compound_coords.is_cuda:
+        raise RuntimeError("fabind_amd: the torsion-space fit runs on a HIP device only (no CPU fallback); got %s"
+                           % predict_compound_coords.device)
+    dev = predict_compound_coords.device
+    ref = reference_compound_coords.detach().to(device=dev)
+    cb = torch.as_tensor(compound_batch).to(dev)
+    if cb.dim() != 1 or cb.numel() != ref.shape[0]:
+        raise ValueError("compound_batch must be [%d]; got %s" % (ref.shape[0], tuple(cb.shape)))
+    if plan is None:
+        raise ValueError("torsion_fit_compound_coords_batched needs the TorsionPlan of the ligands (conformer.rotatable_bonds)")
+    L = int(plan.atom_off.numel()) - 1
+    cb = cb.long()
+    if cb.numel() and (int(cb.min()) < 0 or int(cb.max()) >= L or bool((cb[1:] < cb[:-1]).any())
+                       or not torch.equal(torch.bincount(cb, minlength=L).cumsum(0), plan.atom_off[1:].to(dev).long())):
+        raise ValueError("compound_batch is not sorted or does not match the ligands of `plan`")
+    fit = conformer.fit_conformers(ref, predict_compound_coords, plan, max_iters=max_iters, tol=tol, on_overflow=on_overflow)
+    if predict_compound_coords.dim() == 2:
+        return fit.coords[0], fit.rmsd[0], fit.rmsd0[0]
+    return fit.coords, fit.rmsd, fit.rmsd0
 
 
 def post_optimize_compound_coords(reference_compound_coords, predict_compound_coords, total_epoch=1000, LAS_edge_index=None,

@@ -78,7 +78,8 @@ const char* fabind_last_error(void);
  *     Likewise fabind_pose_pair_rmsd / fabind_pose_cluster (csrc/pose_cluster.hip: the poses of a complex against each other, leader clustering).
  *     Likewise the form report of csrc/norm.hip (fabind_layernorm_rows_form, _rows_bwd_form, fabind_row_stats_form, fabind_edge_lnfold_form /
  *     _blocks, fabind_edge_lnfold_bwd_form, fabind_inter_coord_fold_blocks + FB_LNR_* / FB_LNB_* / FB_RST_* / FB_ELF_* / FB_ELB_*).
- *     Likewise fabind_torsion_plan / fabind_conformer_perturb (csrc/conformer.hip: train-time torsion noise and random rotation).
+ *     Likewise fabind_torsion_plan / fabind_conformer_perturb (csrc/conformer.hip: train-time torsion noise and random rotation)
+ *     and fabind_conformer_fit (csrc/conformer_fit.hip: the start conformer fitted to a pose in torsion space).
  *     Likewise fabind_las_pairs (csrc/topology.hip: LAS constraint pairs from the bond list).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
@@ -521,6 +522,25 @@ int fabind_torsion_plan(const int* nbr_ptr, const int* nbr_idx, const int* nbr_c
 int fabind_conformer_perturb(const float* x, const int* atom_off, int n_ligands, int n_atoms, int n_copies, const int* tor_off,
                              const int* quad, const unsigned* side, const float* angles, int t_total, const float* uniforms,
                              const int* keys, unsigned seed, int relative, int rotate, int centre, float* out, hipStream_t stream);
+/* fabind_conformer_fit (csrc/conformer_fit.hip; a backward-compatible addition under ABI 19): the inverse of fabind_conformer_perturb.
+ *   For every ligand b and every pose s of target fp32 [n_poses, n_atoms, 3]: the angles a of the ligand's torsions (tor_off / quad /
+ *   side as fabind_torsion_plan writes them; tor_off = NULL: none) and the rigid motion for which pose(a) -- the torsions applied to
+ *   x0 fp32 [n_atoms, 3] one after another as relative rotations, the rule of fabind_conformer_perturb, then the optimal proper
+ *   rotation and translation onto the target (Horn's quaternion method in double) -- is closest to the target atom by atom:
+ *   damped Gauss-Newton on E(a) = sum |pose(a) - y|^2 over the T_b torsions and six rigid components (normal matrix and Cholesky in
+ *   double), lam from 1e-3, / 10 (floor 1e-9) after an accepted trial (E fell), * 10 after a rejected one.
+ *   coords fp32 [n_poses, n_atoms, 3] = the fitted pose; angles fp32 [n_poses, t_total] in (-pi, pi], plan order (0 for a ligand
+ *   fitted rigidly only); rmsd0 / rmsd fp32 [n_poses, n_ligands] = sqrt(E / n_b) after the rigid fit alone / at the end; iters int32
+ *   = accepted steps; stop int32 = 0 (an accepted step lowered E by no more than tol E; also: nothing to iterate), 1 (max_iters
+ *   accepted steps), 2 (8 rejections in a row); status int32 [n_ligands] = 0, 3 (more than min(max_atoms, 256) atoms) or 4 (more
+ *   than min(max_torsions, 58) torsions): such a ligand gets the rigid fit only; trace (optional) fp64 [n_poses, n_ligands,
+ *   max_iters] = E after each accepted step, NaN behind the last.  A ligand without atoms writes rmsd 0, iters 0.
+ *   max_atoms / max_torsions (the largest n_b / T_b of the batch, or more) size the work-group's LDS.  One wave per (ligand, pose),
+ *   one launch; every sum in an order fixed by the ligand alone, no atomics: the same bits alone, in any batch, among any poses. */
+int fabind_conformer_fit(const float* x0, const float* target, const int* atom_off, int n_ligands, int n_atoms, int n_poses,
+                         const int* tor_off, const int* quad, const unsigned* side, int t_total, int max_atoms, int max_torsions,
+                         int max_iters, float tol, float* coords, float* angles, float* rmsd0, float* rmsd, int* iters, int* stop,
+                         int* status, double* trace, hipStream_t stream);
 /* LAS ("local atomic structure") constraint pairs of a BATCH of ligands from their bond lists (FABind/fabind/utils/generation_utils.py:
  * 170-187 get_LAS_distance_constraint_mask).  nbr_ptr int32 [sum atoms + 1] / nbr_idx int32 [n_entries] (GLOBAL atom ids): the
  * symmetrised, de-duplicated neighbour lists without self-loops, sorted by owner and then by neighbour; atom_off int32 [n_ligands + 1].

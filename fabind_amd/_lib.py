@@ -128,6 +128,10 @@ SIGNATURES = {
     "fabind_rank_loss_fwd": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp],
     "fabind_pose_pair_rmsd": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
     "fabind_pose_cluster": [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp],
+    "fabind_validity_plan": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp],
+    "fabind_pose_check": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f,
+                          _f, _i, _vp, _vp, _vp],
     "fabind_multi_copy": [_vp, _i, _i, _vp],
     "fabind_adam_chunk": [],
     "fabind_multi_sqnorm": [_vp, _i, _i, _vp, _vp, _vp, _vp],

@@ -1578,3 +1578,27 @@ def pose_cluster(D, conf, threshold):
     check(_lib.load().fabind_pose_cluster(ptr(D), ptr(conf), S, B, float(threshold), ptr(cid), ptr(leader), ptr(size), ptr(ncl), stream()),
           "fabind_pose_cluster")
     return cid, leader, size, ncl
+
+
+def validity_plan_pass(nbr_ptr, nbr_idx, nbr_code, atom_off, n_ligands, z, x0, radii_in, min_volume, auto_flat, auto_off, auto_cnt, counts,
+                       status, offs=None, cls=None, radii=None, pair_ij=None, pair_kind=None, pair_d0=None, group=None, gatoms=None,
+                       centre=None, centre_v0=None):
+    """csrc/pose_check.hip, the plan of fabind_amd.validity.  offs=None: the count pass (counts int32 [B, 4] and status are written); else
+    the write pass into the caller's lists at the offsets offs int32 [4, B + 1]."""
+    check(_lib.load().fabind_validity_plan(ptr(nbr_ptr), ptr(nbr_idx), ptr(nbr_code), ptr(atom_off), int(n_ligands), ptr(z), ptr(x0),
+                                           ptr(radii_in), float(min_volume), ptr(auto_flat), ptr(auto_off), ptr(auto_cnt), ptr(counts),
+                                           ptr(status), ptr(offs), ptr(cls), ptr(radii), ptr(pair_ij), ptr(pair_kind), ptr(pair_d0),
+                                           ptr(group), ptr(gatoms), ptr(centre), ptr(centre_v0), stream()),
+          "fabind_validity_plan(%s)" % ("count" if offs is None else "write"))
+
+
+def pose_check(poses, atom_off, n_ligands, max_atoms, status, cls, radii, offs, pair_ij, pair_kind, pair_d0, group, gatoms, centre, centre_v0,
+               pocket, pocket_off, thresholds, use_ca, stats, flags):
+    """csrc/pose_check.hip: the nine statistics and the flag word of every (ligand, pose) of the fp32 [S, N, 3] poses into stats fp32
+    [B, S, 9] / flags int32 [B, S], one launch.  thresholds = (bond_lo, bond_hi, angle_lo, angle_hi, clash_min, flat_max, ca_min)."""
+    S, N = poses.shape[0], poses.shape[1]
+    t = [float(v) for v in thresholds]
+    check(_lib.load().fabind_pose_check(ptr(poses), int(S), int(N), ptr(atom_off), int(n_ligands), int(max_atoms), ptr(status), ptr(cls),
+                                        ptr(radii), ptr(offs), ptr(pair_ij), ptr(pair_kind), ptr(pair_d0), ptr(group), ptr(gatoms),
+                                        ptr(centre), ptr(centre_v0), ptr(pocket), ptr(pocket_off), t[0], t[1], t[2], t[3], t[4], t[5], t[6],
+                                        int(bool(use_ca)), ptr(stats), ptr(flags), stream()), "fabind_pose_check")

@@ -11,7 +11,11 @@ on [S, B] tensors instead of S text files; they run once per evaluation and are 
 
 `select_distinct_by_confidence` / `distinct_sampling_metrics` are the same evaluation over DISTINCT poses: the leaders of the first
 `top_n` clusters of `fabind_amd.poses.cluster_poses` instead of the `top_n` most confident samples, which are usually one binding mode
-several times."""
+several times.
+
+`select_valid_by_confidence` / `valid_sampling_metrics` are the same evaluation with the physical validity of every pose
+(`fabind_amd.validity.check_poses`) taken into account: valid poses are chosen first, and the table gains the "RMSD < 2 A and valid"
+column docking benchmarks report."""
 import torch
 
 from .models.model import confidence_terms
@@ -129,4 +133,41 @@ def distinct_sampling_metrics(rmsd, cdis, conf, clusters, top_n=1):
         vals += [x.mean(), (x < 2).double().mean(), (x < 5).double().mean()] + [torch.quantile(x, q) for q in (0.25, 0.50, 0.75)]
     names += ["n_clusters_mean", "top_cluster_share"]
     vals += [clusters.n_clusters.double().mean(), clusters.size[0].double().mean() / rmsd.shape[0]]
+    return dict(zip(names, torch.stack(vals).tolist()))
+
+
+def _valid_picks(rmsd, cdis, conf, valid, top_n, who):
+    if rmsd.dim() != 2 or any(tuple(t.shape) != tuple(rmsd.shape) for t in (cdis, conf, valid)):
+        raise ValueError("%s: rmsd, cdis, conf and valid must share one [S, B] shape; got %s, %s, %s, %s"
+                         % (who, tuple(rmsd.shape), tuple(cdis.shape), tuple(conf.shape), tuple(valid.shape)))
+    if not 1 <= int(top_n) <= rmsd.shape[0]:
+        raise ValueError("%s: top_n must be in [1, S = %d]; got %r" % (who, rmsd.shape[0], top_n))
+    order = torch.argsort(conf, dim=0, descending=True, stable=True)
+    invalid = (~valid.bool().gather(0, order)).to(torch.int8)
+    return order.gather(0, torch.argsort(invalid, dim=0, stable=True))[:int(top_n)]
+
+
+def select_valid_by_confidence(rmsd, cdis, conf, valid, top_n=1):
+    """`select_by_confidence` among the VALID poses of each complex: per complex the minimum RMSD and the minimum centroid distance among
+    its `top_n` most confident valid samples; a complex with fewer than `top_n` valid samples is filled with its most confident invalid
+    ones.  rmsd, cdis, conf, valid: [S, B] (`validity.check_poses(...).valid.t()`); equal confidences keep their sample order.
+    -> (rmsd [B], centroid distance [B])."""
+    pick = _valid_picks(rmsd, cdis, conf, valid, top_n, "select_valid_by_confidence")
+    return rmsd.gather(0, pick).min(0).values, cdis.gather(0, pick).min(0).values
+
+
+def valid_sampling_metrics(rmsd, cdis, conf, valid, top_n=1):
+    """The dictionary of `sampling_metrics` on `select_valid_by_confidence`, plus `valid_share` (valid poses over all S * B poses),
+    `top1_valid_share` (complexes whose most confident pose is valid) and `rmsd_lt2_and_valid` (complexes with a chosen pose that is
+    valid and below 2 A: the "RMSD < 2 A and physically valid" column).  -> dict of python floats, one read-back."""
+    pick = _valid_picks(rmsd, cdis, conf, valid, top_n, "valid_sampling_metrics")
+    v = valid.bool()
+    r, c = rmsd.gather(0, pick).min(0).values, cdis.gather(0, pick).min(0).values
+    vals, names = [], []
+    for x, p in ((r.double(), "rmsd"), (c.double(), "centroid_dis")):
+        names += [p + s for s in ("_mean", "_2A", "_5A", "_25", "_50", "_75")]
+        vals += [x.mean(), (x < 2).double().mean(), (x < 5).double().mean()] + [torch.quantile(x, q) for q in (0.25, 0.50, 0.75)]
+    top1 = torch.argsort(conf, dim=0, descending=True, stable=True)[:1]
+    names += ["valid_share", "top1_valid_share", "rmsd_lt2_and_valid"]
+    vals += [v.double().mean(), v.gather(0, top1).double().mean(), (v.gather(0, pick) & (rmsd.gather(0, pick) < 2)).any(0).double().mean()]
     return dict(zip(names, torch.stack(vals).tolist()))

@@ -93,6 +93,33 @@ def torsion_fit_compound_coords_batched(reference_compound_coords, predict_compo
     return fit.coords, fit.rmsd, fit.rmsd0
 
 
+def check_compound_coords_batched(predict_compound_coords, compound_batch, plan, pocket_coords=None, pocket_batch=None, **thresholds):
+    """The physical-validity check of predicted (or post-optimised, or torsion-fitted) ligand coordinates for the inference scripts:
+    `validity.check_poses` (csrc/pose_check.hip) behind the conventions of this module.  predict: [sum Nc, 3] ([S, sum Nc, 3] for S
+    sampled poses); compound_batch: sorted ligand id per atom; plan: the `validity.validity_plan` ValidityPlan of the same ligands;
+    pocket_coords [R, 3] / pocket_batch [R]: the C-alpha atoms of every complex, or None; thresholds: bond_tol, angle_tol, clash_min,
+    flat_max, ca_min as `check_poses` takes them.
+    -> (valid bool [L] ([S, L]), flags int32 [L] ([S, L]), stats float32 [L, 9] ([S, L, 9]))."""
+    from .. import validity
+    if not predict_compound_coords.is_cuda:
+        raise RuntimeError("fabind_amd: the validity check runs on a HIP device only (no CPU fallback); got %s"
+                           % predict_compound_coords.device)
+    if plan is None:
+        raise ValueError("check_compound_coords_batched needs the ValidityPlan of the ligands (validity.validity_plan)")
+    dev = predict_compound_coords.device
+    L = int(plan.atom_off.numel()) - 1
+    cb = torch.as_tensor(compound_batch).to(dev).long()
+    if cb.dim() != 1 or cb.numel() != predict_compound_coords.shape[-2]:
+        raise ValueError("compound_batch must be [%d]; got %s" % (predict_compound_coords.shape[-2], tuple(cb.shape)))
+    if cb.numel() and (int(cb.min()) < 0 or int(cb.max()) >= L or bool((cb[1:] < cb[:-1]).any())
+                       or not torch.equal(torch.bincount(cb, minlength=L).cumsum(0), plan.atom_off[1:].to(dev).long())):
+        raise ValueError("compound_batch is not sorted or does not match the ligands of `plan`")
+    res = validity.check_poses(predict_compound_coords, plan, pocket_coords, pocket_batch, **thresholds)
+    if predict_compound_coords.dim() == 2:
+        return res.valid[:, 0], res.flags[:, 0], res.stats[:, 0]
+    return res.valid.t(), res.flags.t(), res.stats.transpose(0, 1)
+
+
 def post_optimize_compound_coords(reference_compound_coords, predict_compound_coords, total_epoch=1000, LAS_edge_index=None,
                                   mode=0):
     """The reference's per-ligand entry point: -> (x [Nc, 3], loss of the last epoch (float), RMSD (float)).  `mode` only

@@ -81,6 +81,7 @@ const char* fabind_last_error(void);
  *     Likewise fabind_torsion_plan / fabind_conformer_perturb (csrc/conformer.hip: train-time torsion noise and random rotation)
  *     and fabind_conformer_fit (csrc/conformer_fit.hip: the start conformer fitted to a pose in torsion space).
  *     Likewise fabind_las_pairs (csrc/topology.hip: LAS constraint pairs from the bond list).
+ *     Likewise fabind_validity_plan / fabind_pose_check (csrc/pose_check.hip: physical validity of sampled poses).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -592,6 +593,35 @@ int fabind_pose_pair_rmsd(const float* poses, int n_pose, int n_atoms, const int
                           const int* flat, int n_ligands, int max_atoms, float* D, hipStream_t stream);
 int fabind_pose_cluster(const float* D, const float* conf, int n_pose, int n_ligands, float threshold, int* cluster_id, int* leader,
                         int* size, int* n_clusters, hipStream_t stream);
+/* Physical validity of sampled poses (csrc/pose_check.hip; fabind_amd/validity.py documents every layout).  Backward-compatible
+ * additions under ABI 19.
+ * fabind_validity_plan: the per-ligand plan from the coded neighbour lists of fabind_torsion_plan (nbr_ptr / nbr_idx / nbr_code, GLOBAL
+ *   ids, sorted by owner and neighbour), atomic numbers z int32 [sum atoms] and the start conformer x0 fp32 [sum atoms, 3]; radii_in fp32
+ *   [sum atoms] or NULL (Bondi radii by atomic number); auto_flat / auto_off / auto_cnt as fabind_sym_score takes them, or NULL.
+ *   Count mode (offs = NULL): counts int32 [n_ligands, 4] = (ratio pairs, planar groups, group atoms, stereo centres), status int32
+ *   [n_ligands] = 0, 3 (more than 256 atoms) or 5 (a bonded or 1-3 pair at distance 0 in x0): a ligand with status != 0 has no entries.
+ *   Write mode (offs int32 [4, n_ligands + 1] = the exclusive sums of the four counts; status as the count pass left it): cls uint32
+ *   [sum atoms, 16], two bits per pair (i, j) at bit 2 (j % 16) of word j / 16 of row i: 1 bonded, 2 angle, 3 clash, 0 exempt (the
+ *   caller zeroes it); radii fp32 [sum atoms]; pair_ij int32 [pairs, 2] (local i < j, ascending), pair_kind int32 [pairs] (1 / 2),
+ *   pair_d0 fp64 [pairs]; group int32 [groups, 3] = (0 aromatic / 1 double bond, first position in the ligand's slot of gatoms, atoms);
+ *   gatoms int32 [group atoms] local ids; centre int32 [centres, 5] = (c, n1, n2, n3, n4 or -1); centre_v0 fp64 [centres].  A ligand
+ *   whose counts differ from its slots writes no list.  One work-group per ligand, integer work in LDS, no atomics.
+ * fabind_pose_check: stats fp32 [n_ligands, n_pose, 9] = (bond_lo, bond_hi, angle_lo, angle_hi, clash, flat_aromatic, flat_double,
+ *   chirality, ca_dist) and flags int32 [n_ligands, n_pose] (1 BOND, 2 ANGLE, 4 CLASH, 8 AROMATIC_FLAT, 16 DOUBLE_FLAT, 32 CHIRALITY,
+ *   64 PROTEIN, 128 NONFINITE, 256 UNCHECKED) of poses fp32 [n_pose, n_atoms, 3] under the plan; pocket fp32 [residues, 3] with
+ *   pocket_off int32 [n_ligands + 1], or NULL; max_atoms >= every ligand of status 0, <= 256.  One wave per (ligand, pose), one launch
+ *   whatever n_pose; float64 arithmetic on the float32 inputs; an entry is the same bits alone, in any batch and among any n_pose. */
+int fabind_validity_plan(const int* nbr_ptr, const int* nbr_idx, const int* nbr_code, const int* atom_off, int n_ligands,
+                         const int* z, const float* x0, const float* radii_in, float min_volume, const int* auto_flat,
+                         const int* auto_off, const int* auto_cnt, int* counts, int* status, const int* offs, unsigned* cls,
+                         float* radii, int* pair_ij, int* pair_kind, double* pair_d0, int* group, int* gatoms, int* centre,
+                         double* centre_v0, hipStream_t stream);
+int fabind_pose_check(const float* poses, int n_pose, int n_atoms, const int* atom_off, int n_ligands, int max_atoms,
+                      const int* status, const unsigned* cls, const float* radii, const int* offs, const int* pair_ij,
+                      const int* pair_kind, const double* pair_d0, const int* group, const int* gatoms, const int* centre,
+                      const double* centre_v0, const float* pocket, const int* pocket_off, float bond_lo, float bond_hi,
+                      float angle_lo, float angle_hi, float clash_min, float flat_max, float ca_min, int use_ca, float* stats,
+                      int* flags, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross attention (RowAttentionBlock / Attention._attention, models/cross_att.py:118-134,

@@ -1602,3 +1602,27 @@ def pose_check(poses, atom_off, n_ligands, max_atoms, status, cls, radii, offs, 
                                         ptr(radii), ptr(offs), ptr(pair_ij), ptr(pair_kind), ptr(pair_d0), ptr(group), ptr(gatoms),
                                         ptr(centre), ptr(centre_v0), ptr(pocket), ptr(pocket_off), t[0], t[1], t[2], t[3], t[4], t[5], t[6],
                                         int(bool(use_ca)), ptr(stats), ptr(flags), stream()), "fabind_pose_check")
+
+
+def protein_grid_pass(prot_xyz, prot_z, prot_off, n_complex, radii_in, edge, origin, dims, status, counts=None, cell_off=None, kept_off=None,
+                      n_cells=0, n_kept=0, cell_of=None, cell_fill=None, slot=None, cell_ptr=None, xyz=None, radii=None, atom_id=None):
+    """csrc/protein_contacts.hip, the cell list of fabind_amd.validity.protein_grid.  cell_off=None: the count pass (origin, dims, status
+    and counts int32 [B, 2] = (cells, kept atoms) are written); else the write pass into the caller's lists at cell_off / kept_off."""
+    check(_lib.load().fabind_protein_grid(ptr(prot_xyz), ptr(prot_z), ptr(prot_off), int(n_complex), ptr(radii_in), float(edge), ptr(origin),
+                                          ptr(dims), ptr(status), ptr(counts), ptr(cell_off), ptr(kept_off), int(n_cells), int(n_kept),
+                                          ptr(cell_of), ptr(cell_fill), ptr(slot), ptr(cell_ptr), ptr(xyz), ptr(radii), ptr(atom_id), stream()),
+          "fabind_protein_grid(%s)" % ("count" if cell_off is None else "write"))
+
+
+def pose_protein_check(poses, atom_off, n_complex, max_atoms, plan_status, lig_radii, grid_status, origin, dims, cell_off, kept_off, cell_ptr,
+                       xyz, radii, atom_id, edge, thresholds, max_radius, stats, counts, pair, flags):
+    """csrc/protein_contacts.hip: the three statistics, three counts, the closest pair and the flag word of every (complex, pose) of the
+    fp32 [S, N, 3] poses into stats fp32 [B, S, 3] / counts int32 [B, S, 3] / pair int32 [B, S, 2] / flags int32 [B, S], one launch.
+    thresholds = (cutoff, clash_min, overlap_max, vdw_scale, spacing)."""
+    S, N = poses.shape[0], poses.shape[1]
+    t = [float(v) for v in thresholds]
+    check(_lib.load().fabind_pose_protein_check(ptr(poses), int(S), int(N), ptr(atom_off), int(n_complex), int(max_atoms), ptr(plan_status),
+                                                ptr(lig_radii), ptr(grid_status), ptr(origin), ptr(dims), ptr(cell_off), ptr(kept_off),
+                                                ptr(cell_ptr), ptr(xyz), ptr(radii), ptr(atom_id), float(edge), t[0], t[1], t[2], t[3], t[4],
+                                                float(max_radius), ptr(stats), ptr(counts), ptr(pair), ptr(flags), stream()),
+          "fabind_pose_protein_check")

@@ -120,6 +120,34 @@ def check_compound_coords_batched(predict_compound_coords, compound_batch, plan,
     return res.valid.t(), res.flags.t(), res.stats.transpose(0, 1)
 
 
+def check_protein_contacts_batched(predict_compound_coords, compound_batch, plan, grid, **thresholds):
+    """Predicted (or post-optimised, or torsion-fitted) ligand coordinates against ALL heavy atoms of their proteins for the inference
+    scripts: `validity.check_poses_protein` (csrc/protein_contacts.hip) behind the conventions of this module.  predict: [sum Nc, 3]
+    ([S, sum Nc, 3] for S sampled poses); compound_batch: sorted ligand id per atom; plan: the `validity.validity_plan` ValidityPlan of
+    the ligands; grid: the `validity.protein_grid` ProteinGrid of the same complexes (`validity.protein_atoms_from_pdb` reads its atoms);
+    thresholds: cutoff, clash_min, overlap_max, vdw_scale, spacing as `check_poses_protein` takes them.
+    -> (ok bool [L] ([S, L]), flags int32 [L] ([S, L]), stats float32 [L, 3] ([S, L, 3])); `ok & valid` with the `valid` of
+    `check_compound_coords_batched` is the "physically valid" of the docking benchmarks."""
+    from .. import validity
+    if not predict_compound_coords.is_cuda:
+        raise RuntimeError("fabind_amd: the protein-contact check runs on a HIP device only (no CPU fallback); got %s"
+                           % predict_compound_coords.device)
+    if plan is None or grid is None:
+        raise ValueError("check_protein_contacts_batched needs the ValidityPlan of the ligands and the ProteinGrid of their proteins")
+    dev = predict_compound_coords.device
+    L = int(plan.atom_off.numel()) - 1
+    cb = torch.as_tensor(compound_batch).to(dev).long()
+    if cb.dim() != 1 or cb.numel() != predict_compound_coords.shape[-2]:
+        raise ValueError("compound_batch must be [%d]; got %s" % (predict_compound_coords.shape[-2], tuple(cb.shape)))
+    if cb.numel() and (int(cb.min()) < 0 or int(cb.max()) >= L or bool((cb[1:] < cb[:-1]).any())
+                       or not torch.equal(torch.bincount(cb, minlength=L).cumsum(0), plan.atom_off[1:].to(dev).long())):
+        raise ValueError("compound_batch is not sorted or does not match the ligands of `plan`")
+    res = validity.check_poses_protein(predict_compound_coords, plan, grid, **thresholds)
+    if predict_compound_coords.dim() == 2:
+        return res.ok[:, 0], res.flags[:, 0], res.stats[:, 0]
+    return res.ok.t(), res.flags.t(), res.stats.transpose(0, 1)
+
+
 def post_optimize_compound_coords(reference_compound_coords, predict_compound_coords, total_epoch=1000, LAS_edge_index=None,
                                   mode=0):
     """The reference's per-ligand entry point: -> (x [Nc, 3], loss of the last epoch (float), RMSD (float)).  `mode` only

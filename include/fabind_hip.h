@@ -82,6 +82,7 @@ const char* fabind_last_error(void);
  *     and fabind_conformer_fit (csrc/conformer_fit.hip: the start conformer fitted to a pose in torsion space).
  *     Likewise fabind_las_pairs (csrc/topology.hip: LAS constraint pairs from the bond list).
  *     Likewise fabind_validity_plan / fabind_pose_check (csrc/pose_check.hip: physical validity of sampled poses).
+ *     Likewise fabind_protein_grid / fabind_pose_protein_check (csrc/protein_contacts.hip: poses against all protein heavy atoms).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -622,6 +623,36 @@ int fabind_pose_check(const float* poses, int n_pose, int n_atoms, const int* at
                       const double* centre_v0, const float* pocket, const int* pocket_off, float bond_lo, float bond_hi,
                       float angle_lo, float angle_hi, float clash_min, float flat_max, float ca_min, int use_ca, float* stats,
                       int* flags, hipStream_t stream);
+/* Sampled poses against all heavy atoms of the protein (csrc/protein_contacts.hip; fabind_amd/validity.py documents every layout).
+ * Backward-compatible additions under ABI 19.
+ * fabind_protein_grid: a cell list per complex of prot_xyz fp32 [sum atoms, 3], prot_z int32 [sum atoms], prot_off int32
+ *   [n_complex + 1]; radii_in fp32 [sum atoms] or NULL (Bondi radii by atomic number).  The cell of an atom along an axis is
+ *   floor(double(x) / double(edge)) clamped to +-2^29; atoms with z <= 1 are dropped.
+ *   Count mode (cell_off = NULL): origin int32 [n_complex, 3] (lowest cell), dims int32 [n_complex, 3], status int32 [n_complex] = 0,
+ *   6 (a non-finite coordinate) or 7 (a box of more than 2^20 cells), counts int32 [n_complex, 2] = (cells, kept atoms); a complex with
+ *   status != 0 has origin = dims = 0 and no entries.
+ *   Write mode (cell_off / kept_off int32 [n_complex + 1] = the exclusive sums of the two counts, n_cells / n_kept their totals; origin,
+ *   dims and status as the count pass left them): cell_ptr int32 [n_cells + 1], positions into the sorted atoms; xyz fp32 [n_kept, 3],
+ *   radii fp32 [n_kept], atom_id int32 [n_kept] (the id within the complex), ordered by (complex, cell, id).  Scratch: cell_of int32
+ *   [sum atoms], cell_fill int32 [n_cells], slot int32 [n_kept].  Integer atomics build the histogram and fill the cells; the order
+ *   within a cell is by id whatever the scheduling.
+ * fabind_pose_protein_check: stats fp32 [n_complex, n_pose, 3] = (prot_clash, prot_dist, overlap), counts int32 [n_complex, n_pose, 3] =
+ *   (n_close, n_lig, n_both), pair int32 [n_complex, n_pose, 2] = (ligand atom, protein atom) of the prot_clash minimum or (-1, -1),
+ *   flags int32 [n_complex, n_pose] (1 PROTEIN_CLASH, 2 PROTEIN_OVERLAP, 128 NONFINITE, 256 UNCHECKED) of poses fp32 [n_pose, n_atoms, 3]
+ *   of the ligands atom_off int32 [n_complex + 1] with radii lig_radii fp32 [n_atoms] and status plan_status (fabind_validity_plan)
+ *   against the grid; max_atoms >= every ligand of status 0, <= 256; max_radius >= every protein radius, cutoff <= edge and
+ *   vdw_scale * max_radius <= edge.  One wave per (complex, pose), one launch whatever n_pose; float64 arithmetic on the float32 inputs;
+ *   an entry is the same bits alone, in any batch and among any n_pose. */
+int fabind_protein_grid(const float* prot_xyz, const int* prot_z, const int* prot_off, int n_complex, const float* radii_in, float edge,
+                        int* origin, int* dims, int* status, int* counts, const int* cell_off, const int* kept_off, int n_cells,
+                        int n_kept, int* cell_of, int* cell_fill, int* slot, int* cell_ptr, float* xyz, float* radii, int* atom_id,
+                        hipStream_t stream);
+int fabind_pose_protein_check(const float* poses, int n_pose, int n_atoms, const int* atom_off, int n_complex, int max_atoms,
+                              const int* plan_status, const float* lig_radii, const int* grid_status, const int* origin,
+                              const int* dims, const int* cell_off, const int* kept_off, const int* cell_ptr, const float* xyz,
+                              const float* radii, const int* atom_id, float edge, float cutoff, float clash_min, float overlap_max,
+                              float vdw_scale, float spacing, float max_radius, float* stats, int* counts, int* pair, int* flags,
+                              hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross attention (RowAttentionBlock / Attention._attention, models/cross_att.py:118-134,

@@ -135,6 +135,8 @@ SIGNATURES = {
     "fabind_protein_grid": [_vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_pose_protein_check": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f,
                                   _vp, _vp, _vp, _vp, _vp],
+    "fabind_pose_relax": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f,
+                          _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_multi_copy": [_vp, _i, _i, _vp],
     "fabind_adam_chunk": [],
     "fabind_multi_sqnorm": [_vp, _i, _i, _vp, _vp, _vp, _vp],

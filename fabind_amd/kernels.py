@@ -1626,3 +1626,18 @@ def pose_protein_check(poses, atom_off, n_complex, max_atoms, plan_status, lig_r
                                                 ptr(cell_ptr), ptr(xyz), ptr(radii), ptr(atom_id), float(edge), t[0], t[1], t[2], t[3], t[4],
                                                 float(max_radius), ptr(stats), ptr(counts), ptr(pair), ptr(flags), stream()),
           "fabind_pose_protein_check")
+
+
+def pose_relax(x0, target, angles0, atom_off, n_complex, tor_off, quad, side, t_total, max_atoms, max_torsions, plan_status, cls, lig_radii,
+               grid_status, origin, dims, cell_off, kept_off, cell_ptr, prot_xyz, prot_radii, edge, max_reach, weights, max_iters, tol, coords,
+               angles, energy0, energy, iters, stop, status, trace):
+    """csrc/pose_relax.hip: every (complex, pose) of the fp32 [S, N, 3] targets relaxed in torsion space, one launch.  weights = (w_fit,
+    w_prot, w_intra, c_prot, c_intra); tor_off=None: rigid only; plan_status=None: no intra term; grid_status=None: no protein term."""
+    S, N = target.shape[0], target.shape[1]
+    w = [float(v) for v in weights]
+    check(_lib.load().fabind_pose_relax(ptr(x0), ptr(target), ptr(angles0), ptr(atom_off), int(n_complex), int(N), int(S), ptr(tor_off),
+                                        ptr(quad), ptr(side), int(t_total), int(max_atoms), int(max_torsions), ptr(plan_status), ptr(cls),
+                                        ptr(lig_radii), ptr(grid_status), ptr(origin), ptr(dims), ptr(cell_off), ptr(kept_off), ptr(cell_ptr),
+                                        ptr(prot_xyz), ptr(prot_radii), float(edge), float(max_reach), w[0], w[1], w[2], w[3], w[4],
+                                        int(max_iters), float(tol), ptr(coords), ptr(angles), ptr(energy0), ptr(energy), ptr(iters), ptr(stop),
+                                        ptr(status), ptr(trace), stream()), "fabind_pose_relax")

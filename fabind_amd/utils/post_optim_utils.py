@@ -4,7 +4,8 @@ fabind_inference.py:285-328).
 `post_optimize_compound_coords` keeps the reference's name, arguments and return triple for ONE ligand;
 `post_optimize_compound_coords_batched` runs a whole batch of ligands in one kernel launch (csrc/post_optim.hip: one
 work-group per ligand, all Adam iterations inside the kernel).  HIP device tensors only -- there is no CPU fallback.
-`torsion_fit_compound_coords_batched` has no counterpart in the reference: it moves only what a molecule can move.
+`torsion_fit_compound_coords_batched` has no counterpart in the reference: it moves only what a molecule can move;
+`relax_compound_coords_batched` then moves it out of contact with the protein.
 
 Numerics: the objective is non-smooth (|.| and relu) and Adam moves each coordinate by ~lr = 0.1 A per step, so the
 iteration is chaotic: the reference's own result changes by ~0.1 A between its two `torch.cdist` code paths (direct
@@ -63,14 +64,15 @@ def post_optimize_compound_coords_batched(reference_compound_coords, predict_com
 
 
 def torsion_fit_compound_coords_batched(reference_compound_coords, predict_compound_coords, compound_batch, plan, max_iters=50, tol=1e-6,
-                                        on_overflow="truncate"):
+                                        on_overflow="truncate", return_fit=False):
     """The torsion-space counterpart of `post_optimize_compound_coords_batched`: instead of pulling the predicted cloud towards the
     start conformer's LAS distances, the start conformer itself is fitted to the prediction over its rotatable-bond dihedrals and
     one rigid motion (`conformer.fit_conformers`, csrc/conformer_fit.hip), so bond lengths, angles and rings are exactly the start
     conformer's.  reference / predict: [sum Nc, 3] ([S, sum Nc, 3] for S sampled poses); compound_batch: sorted ligand id per atom;
     plan: the `conformer.rotatable_bonds` TorsionPlan of the same ligands.  A ligand beyond the kernel's limits (256 atoms, 58
     torsions) is fitted rigidly (`on_overflow`).
-    -> (x like predict, rmsd_to_prediction [L] ([S, L]), rmsd_rigid [L] ([S, L]): the same after the rigid fit alone)."""
+    -> (x like predict, rmsd_to_prediction [L] ([S, L]), rmsd_rigid [L] ([S, L]): the same after the rigid fit alone); with return_fit
+    the `conformer.ConformerFit` itself (its angles start `relax_compound_coords_batched`)."""
     from .. import conformer
     if not predict_compound_coords.is_cuda:
         raise RuntimeError("fabind_amd: the torsion-space fit runs on a HIP device only (no CPU fallback); got %s"
@@ -88,9 +90,34 @@ def torsion_fit_compound_coords_batched(reference_compound_coords, predict_compo
                        or not torch.equal(torch.bincount(cb, minlength=L).cumsum(0), plan.atom_off[1:].to(dev).long())):
         raise ValueError("compound_batch is not sorted or does not match the ligands of `plan`")
     fit = conformer.fit_conformers(ref, predict_compound_coords, plan, max_iters=max_iters, tol=tol, on_overflow=on_overflow)
+    if return_fit:
+        return fit
     if predict_compound_coords.dim() == 2:
         return fit.coords[0], fit.rmsd[0], fit.rmsd0[0]
     return fit.coords, fit.rmsd, fit.rmsd0
+
+
+def relax_compound_coords_batched(reference_compound_coords, predict_compound_coords, compound_batch, plan, validity_plan, grid,
+                                  fit_iters=50, max_iters=100, tol=1e-6, on_overflow="truncate", **weights):
+    """`torsion_fit_compound_coords_batched` followed by the relaxation out of protein and internal clashes (`relax.relax_poses`,
+    csrc/pose_relax.hip): the start conformer is fitted to the prediction in torsion space, then moved over the same torsions and one
+    rigid motion, held to the prediction and pushed out of contact with all heavy atoms of the protein and with itself.  reference /
+    predict: [sum Nc, 3] ([S, sum Nc, 3] for S sampled poses), predict in the frame of the grid; compound_batch: sorted ligand id per
+    atom; plan: the `conformer.rotatable_bonds` TorsionPlan, validity_plan: the `validity.validity_plan` ValidityPlan, grid: the
+    `validity.protein_grid` ProteinGrid of the same complexes; weights: w_fit, w_prot, w_intra, c_prot, c_intra as `relax_poses` takes
+    them.  A ligand beyond the kernels' limits is fitted rigidly and left there (256 atoms) or relaxed rigidly (58 torsions).
+    -> (x like predict, energy float64 [L, 3] ([S, L, 3]): the unweighted fit / protein / intra sums at the end, energy0: the same
+    at the fitted pose)."""
+    from .. import relax
+    if validity_plan is None or grid is None:
+        raise ValueError("relax_compound_coords_batched needs the ValidityPlan of the ligands and the ProteinGrid of their proteins")
+    fit = torsion_fit_compound_coords_batched(reference_compound_coords, predict_compound_coords, compound_batch, plan, max_iters=fit_iters,
+                                              tol=tol, on_overflow=on_overflow, return_fit=True)
+    res = relax.relax_poses(reference_compound_coords.detach().to(predict_compound_coords.device), predict_compound_coords, plan, validity_plan,
+                            grid, angles0=fit.angles, max_iters=max_iters, tol=tol, on_overflow=on_overflow, **weights)
+    if predict_compound_coords.dim() == 2:
+        return res.coords[0], res.energy[0], res.energy0[0]
+    return res.coords, res.energy, res.energy0
 
 
 def check_compound_coords_batched(predict_compound_coords, compound_batch, plan, pocket_coords=None, pocket_batch=None, **thresholds):

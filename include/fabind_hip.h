@@ -83,6 +83,7 @@ const char* fabind_last_error(void);
  *     Likewise fabind_las_pairs (csrc/topology.hip: LAS constraint pairs from the bond list).
  *     Likewise fabind_validity_plan / fabind_pose_check (csrc/pose_check.hip: physical validity of sampled poses).
  *     Likewise fabind_protein_grid / fabind_pose_protein_check (csrc/protein_contacts.hip: poses against all protein heavy atoms).
+ *     Likewise fabind_pose_relax (csrc/pose_relax.hip: poses relaxed out of protein and internal clashes in torsion space).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -653,6 +654,27 @@ int fabind_pose_protein_check(const float* poses, int n_pose, int n_atoms, const
                               const float* radii, const int* atom_id, float edge, float cutoff, float clash_min, float overlap_max,
                               float vdw_scale, float spacing, float max_radius, float* stats, int* counts, int* pair, int* flags,
                               hipStream_t stream);
+/* fabind_pose_relax (csrc/pose_relax.hip; a backward-compatible addition under ABI 19; fabind_amd/relax.py documents every layout): the
+ * start conformer x0 fp32 [n_atoms, 3] of every ligand moved over its torsions (tor_off / quad / side of fabind_torsion_plan, t_total
+ * rows; tor_off = NULL: rigid only) and one rigid motion, held to target fp32 [n_poses, n_atoms, 3] and pushed out of contact with the
+ * kept protein atoms of the complex's cell list (fabind_protein_grid; grid_status = NULL or != 0: no protein term, status bit 16) and
+ * out of its own PAIR_CLASH pairs (plan_status / cls uint32 [n_atoms, 16] / lig_radii of fabind_validity_plan; plan_status = NULL or
+ * != 0: no intra term, status bit 8): damped Gauss-Newton on E = w_fit sum |X - y|^2 + w_prot sum max(0, c_prot (r_i + r_p) - d)^2 +
+ * w_intra sum max(0, c_intra (r_i + r_j) - d)^2, started at angles0 fp32 [n_poses, t_total] (NULL: zeros) and the Horn fit onto the
+ * target.  max_reach = c_prot * (largest ligand radius + largest protein radius) <= edge.  One wave per (complex, pose), one launch.
+ * coords fp32 [n_poses, n_atoms, 3]; angles fp32 [n_poses, t_total] in (-pi, pi]; energy0 / energy fp64 [n_poses, n_complex, 3] = the
+ * three unweighted sums at the start / the end; iters int32 [n_poses, n_complex] accepted steps; stop int32 [n_poses, n_complex] = 0
+ * converged (E - E' <= tol E), 1 max_iters, 2 eight rejections in a row, 3 a non-finite input (NaN outputs); status int32 [n_complex] =
+ * 0, 3 (more than 256 atoms: the Horn image, the last two sums NaN) or 4 (more than 58 torsions: relaxed rigidly, zero angles), plus
+ * the bits 8 and 16; trace fp64 [n_poses, n_complex, max_iters] or NULL: E after each accepted step, NaN behind the last.  An entry is
+ * the same bits alone, in any batch, among any n_poses and on a repeat. */
+int fabind_pose_relax(const float* x0, const float* target, const float* angles0, const int* atom_off, int n_complex, int n_atoms,
+                      int n_poses, const int* tor_off, const int* quad, const unsigned* side, int t_total, int max_atoms, int max_torsions,
+                      const int* plan_status, const unsigned* cls, const float* lig_radii, const int* grid_status, const int* origin,
+                      const int* dims, const int* cell_off, const int* kept_off, const int* cell_ptr, const float* prot_xyz,
+                      const float* prot_radii, float edge, float max_reach, float w_fit, float w_prot, float w_intra, float c_prot,
+                      float c_intra, int max_iters, float tol, float* coords, float* angles, double* energy0, double* energy, int* iters,
+                      int* stop, int* status, double* trace, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross attention (RowAttentionBlock / Attention._attention, models/cross_att.py:118-134,

@@ -1641,3 +1641,26 @@ def pose_relax(x0, target, angles0, atom_off, n_complex, tor_off, quad, side, t_
                                         ptr(prot_xyz), ptr(prot_radii), float(edge), float(max_reach), w[0], w[1], w[2], w[3], w[4],
                                         int(max_iters), float(tol), ptr(coords), ptr(angles), ptr(energy0), ptr(energy), ptr(iters), ptr(stop),
                                         ptr(status), ptr(trace), stream()), "fabind_pose_relax")
+
+
+def embed_bounds_pass(nbr_ptr, nbr_idx, nbr_code, atom_off, n_ligands, z, chiral_sign, volumes, counts, status, quad_off=None, mat_off=None,
+                      bounds=None, geom=None, quads=None, quad_lo=None, quad_hi=None):
+    """csrc/embed.hip, the distance bounds of fabind_amd.embed.  quad_off=None: the count pass (counts int32 [B] and status are written);
+    else the write pass into the caller's lists at quad_off int32 [B + 1] / mat_off int64 [B + 1].  volumes = (v_flat, v_min, v_max)."""
+    v = [float(x) for x in volumes]
+    check(_lib.load().fabind_embed_bounds(ptr(nbr_ptr), ptr(nbr_idx), ptr(nbr_code), ptr(atom_off), int(n_ligands), ptr(z), ptr(chiral_sign),
+                                          v[0], v[1], v[2], ptr(counts), ptr(status), ptr(quad_off), ptr(mat_off), ptr(bounds), ptr(geom),
+                                          ptr(quads), ptr(quad_lo), ptr(quad_hi), stream()),
+          "fabind_embed_bounds(%s)" % ("count" if quad_off is None else "write"))
+
+
+def embed_conformers(bounds, mat_off, atom_off, n_ligands, n_atoms, n_confs, plan_status, quad_off, quads, quad_lo, quad_hi, keys, seed,
+                     max_tries, max_steps, power_iters, tolerances, coords, status, tries, steps, viol, energy, trace):
+    """csrc/embed.hip: n_confs conformers of every ligand under its bounds into coords fp32 [n_confs, N, 3], one launch.  tolerances =
+    (viol_tol, v_tol, w_v, w4)."""
+    w = [float(x) for x in tolerances]
+    check(_lib.load().fabind_embed_conformers(ptr(bounds), ptr(mat_off), ptr(atom_off), int(n_ligands), int(n_atoms), int(n_confs),
+                                              ptr(plan_status), ptr(quad_off), ptr(quads), ptr(quad_lo), ptr(quad_hi), ptr(keys),
+                                              int(seed) & 0xFFFFFFFF, int(max_tries), int(max_steps), int(power_iters), w[0], w[1], w[2], w[3],
+                                              ptr(coords), ptr(status), ptr(tries), ptr(steps), ptr(viol), ptr(energy), ptr(trace), stream()),
+          "fabind_embed_conformers")

@@ -84,6 +84,7 @@ const char* fabind_last_error(void);
  *     Likewise fabind_validity_plan / fabind_pose_check (csrc/pose_check.hip: physical validity of sampled poses).
  *     Likewise fabind_protein_grid / fabind_pose_protein_check (csrc/protein_contacts.hip: poses against all protein heavy atoms).
  *     Likewise fabind_pose_relax (csrc/pose_relax.hip: poses relaxed out of protein and internal clashes in torsion space).
+ *     Likewise fabind_embed_bounds / fabind_embed_conformers (csrc/embed.hip: start conformers from the bond list by distance geometry).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -675,6 +676,32 @@ int fabind_pose_relax(const float* x0, const float* target, const float* angles0
                       const float* prot_radii, float edge, float max_reach, float w_fit, float w_prot, float w_intra, float c_prot,
                       float c_intra, int max_iters, float tol, float* coords, float* angles, double* energy0, double* energy, int* iters,
                       int* stop, int* status, double* trace, hipStream_t stream);
+/* Start conformers from the bond list by distance geometry (csrc/embed.hip; fabind_amd/embed.py documents every layout and DESIGN.md
+ * section 20 every rule).  Backward-compatible additions under ABI 19.
+ * fabind_embed_bounds: per ligand (at most 256 heavy atoms) from the coded neighbour lists of fabind_torsion_plan and the atomic numbers z
+ *   int32 [sum atoms]; chiral_sign int32 [sum atoms] (+1 / -1: the wanted sign of the stereo centre's signed volume, anything else:
+ *   none) or NULL.  Count mode (quad_off = NULL): counts int32 [n_ligands] = signed-volume terms, status int32 [n_ligands] = 0 or 3 (more
+ *   than 256 atoms: no entries).  Write mode (quad_off int32 [n_ligands + 1] = the exclusive sums of the counts, mat_off int64
+ *   [n_ligands + 1] = the exclusive sums of n^2 over the ligands of status 0; status as the count pass left it): bounds fp32, one n x n
+ *   block per ligand at mat_off (upper bound of (i, j) at (min, max), lower at (max, min), diagonal 0), triangle-smoothed in float32;
+ *   geom int32 [sum atoms] = 0 TETRA / 1 TRIGONAL / 2 LINEAR; quads int32 [terms, 4] local ids with quad_lo / quad_hi fp32 [terms]: the
+ *   interval of V = det[p1 - p0, p2 - p0, p3 - p0] (flat terms +-v_flat, stereo terms sign * [v_min, v_max]); status becomes 6 where
+ *   some lower bound exceeds its upper bound after smoothing.  One work-group per ligand, no atomics.
+ * fabind_embed_conformers: n_confs conformers of every ligand of status 0 under the bounds, one work-group per (ligand, conformer), every
+ *   try and minimisation step inside the one launch.  keys uint32 [n_ligands]; coords fp32 [n_confs, n_atoms, 3] centred on the
+ *   centroid; status int32 [n_ligands, n_confs] = 0, 1 (max_tries exhausted: the try of the smallest largest violation) or the plan's
+ *   3 / 6 (zero rows); tries / steps int32, viol (largest pair violation, A) / energy fp64 [n_ligands, n_confs], all of the RETURNED
+ *   coordinates; trace fp64 [n_ligands, n_confs, max_steps + 1] or NULL: E after each step of the last try, NaN behind the last.  An
+ *   entry is the same bits alone, in any batch, among any n_confs and on a repeat. */
+int fabind_embed_bounds(const int* nbr_ptr, const int* nbr_idx, const int* nbr_code, const int* atom_off, int n_ligands, const int* z,
+                        const int* chiral_sign, float v_flat, float v_min, float v_max, int* counts, int* status, const int* quad_off,
+                        const long long* mat_off, float* bounds, int* geom, int* quads, float* quad_lo, float* quad_hi,
+                        hipStream_t stream);
+int fabind_embed_conformers(const float* bounds, const long long* mat_off, const int* atom_off, int n_ligands, int n_atoms, int n_confs,
+                            const int* plan_status, const int* quad_off, const int* quads, const float* quad_lo, const float* quad_hi,
+                            const unsigned* keys, unsigned seed, int max_tries, int max_steps, int power_iters, float viol_tol,
+                            float v_tol, float w_v, float w4, float* coords, int* status, int* tries, int* steps, double* viol,
+                            double* energy, double* trace, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross attention (RowAttentionBlock / Attention._attention, models/cross_att.py:118-134,

@@ -140,6 +140,8 @@ SIGNATURES = {
     "fabind_embed_bounds": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_embed_conformers": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, _i, _i, _i, _f, _f, _f, _f, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _vp],
+    "fabind_conformer_pair_rmsd": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp],
+    "fabind_conformer_cross_rmsd": [_vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp],
     "fabind_multi_copy": [_vp, _i, _i, _vp],
     "fabind_adam_chunk": [],
     "fabind_multi_sqnorm": [_vp, _i, _i, _vp, _vp, _vp, _vp],

@@ -1568,6 +1568,29 @@ def pose_pair_rmsd(poses, aoff, flat_off, use_cnt, flat, B, max_atoms):
     return D
 
 
+def conformer_pair_rmsd(coords, aoff, flat_off, use_cnt, flat, B, max_atoms):
+    """D [B, S, S] of csrc/conformer_rmsd.hip: the superposed (symmetry-corrected) RMSD of every pair of the fp32 [S, N, 3] conformers."""
+    S, N = coords.shape[0], coords.shape[1]
+    D = torch.empty((B, S, S), dtype=torch.float32, device=coords.device)
+    check(_lib.load().fabind_conformer_pair_rmsd(ptr(coords), S, N, ptr(aoff), ptr(flat_off), ptr(use_cnt), ptr(flat), B, max_atoms,
+                                                 ptr(D), stream()), "fabind_conformer_pair_rmsd")
+    return D
+
+
+def conformer_cross_rmsd(coords, ref, aoff, flat_off, use_cnt, flat, B, max_atoms, with_fit):
+    """D [B, S, T] of csrc/conformer_rmsd.hip: fp32 [S, N, 3] conformers against fp32 [T, N, 3] references; with_fit also the
+    minimising automorphism int32 [B, S, T], the unit quaternion fp64 [B, S, T, 4] and the translation fp64 [B, S, T, 3] (else None)."""
+    S, N, T = coords.shape[0], coords.shape[1], ref.shape[0]
+    dev = coords.device
+    D = torch.empty((B, S, T), dtype=torch.float32, device=dev)
+    k = torch.empty((B, S, T), dtype=torch.int32, device=dev) if with_fit else None
+    q = torch.empty((B, S, T, 4), dtype=torch.float64, device=dev) if with_fit else None
+    t = torch.empty((B, S, T, 3), dtype=torch.float64, device=dev) if with_fit else None
+    check(_lib.load().fabind_conformer_cross_rmsd(ptr(coords), S, ptr(ref), T, N, ptr(aoff), ptr(flat_off), ptr(use_cnt), ptr(flat), B,
+                                                  max_atoms, ptr(D), ptr(k), ptr(q), ptr(t), stream()), "fabind_conformer_cross_rmsd")
+    return D, k, q, t
+
+
 def pose_cluster(D, conf, threshold):
     """Leader clustering (csrc/pose_cluster.hip) of D fp32 [B, S, S] under conf fp32 [S, B] -> int32 cluster_id, leader, size [S, B]
     and n_clusters [B]."""

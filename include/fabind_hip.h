@@ -85,6 +85,7 @@ const char* fabind_last_error(void);
  *     Likewise fabind_protein_grid / fabind_pose_protein_check (csrc/protein_contacts.hip: poses against all protein heavy atoms).
  *     Likewise fabind_pose_relax (csrc/pose_relax.hip: poses relaxed out of protein and internal clashes in torsion space).
  *     Likewise fabind_embed_bounds / fabind_embed_conformers (csrc/embed.hip: start conformers from the bond list by distance geometry).
+ *     Likewise fabind_conformer_pair_rmsd / fabind_conformer_cross_rmsd (csrc/conformer_rmsd.hip: superposed symmetric RMSD of conformers).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -702,6 +703,25 @@ int fabind_embed_conformers(const float* bounds, const long long* mat_off, const
                             const unsigned* keys, unsigned seed, int max_tries, int max_steps, int power_iters, float viol_tol,
                             float v_tol, float w_v, float w4, float* coords, int* status, int* tries, int* steps, double* viol,
                             double* energy, double* trace, hipStream_t stream);
+/* Conformers of every ligand against each other or against reference conformers after the best rigid superposition
+ * (csrc/conformer_rmsd.hip).  Backward-compatible additions under ABI 19.
+ *   D = sqrt(min_k max(0, G_s + G_t - 2 lambda_k) / n_b): G the sums of squared distances to the own centroid, lambda_k the largest
+ *   eigenvalue of Horn's 4 x 4 matrix of S_k = sum_i (x_s[a_k[i]] - c_s)(y_t[i] - c_t)^T, a_k the automorphisms of ligand b (atom_off,
+ *   flat_off, auto_cnt, flat as fabind_pose_pair_rmsd takes them: auto_cnt[b] = 0 is the identity alone, an entry outside [0, n_b)
+ *   counts as i).  Proper rotations only.  Centroids, centred coordinates, sums and the eigen-solve are double; D is fp32.
+ * fabind_conformer_pair_rmsd: X fp32 [n_conf, n_atoms, 3] against itself -> D [n_ligands, n_conf, n_conf], every unordered pair computed
+ *   once and mirrored, the diagonal +0.0.
+ * fabind_conformer_cross_rmsd: X against Y fp32 [n_ref, n_atoms, 3] -> D [n_ligands, n_conf, n_ref] and, when auto_index / quat / trans
+ *   are given (all three or none), per entry the minimising k (int32, the lowest on equal values), Horn's unit quaternion (w, x, y, z)
+ *   fp64 [.., 4] and trans = c_t - R(q) c_s fp64 [.., 3]: R(q) x_s[a_k[i]] + trans is x_s superposed on y_t.
+ * A ligand without atoms gets 0 (identity fit); one with more than max_atoms atoms gets NaN; a non-finite coordinate makes every entry of
+ * its conformer NaN and no other.  An entry is the same bits alone, in any batch, among any n_conf / n_ref and on a repeat; no atomics.
+ * n_conf, n_ref <= 512 and max_atoms (>= every n_b) <= 2048, refused otherwise before anything is launched. */
+int fabind_conformer_pair_rmsd(const float* X, int n_conf, int n_atoms, const int* atom_off, const int* flat_off, const int* auto_cnt,
+                               const int* flat, int n_ligands, int max_atoms, float* D, hipStream_t stream);
+int fabind_conformer_cross_rmsd(const float* X, int n_conf, const float* Y, int n_ref, int n_atoms, const int* atom_off,
+                                const int* flat_off, const int* auto_cnt, const int* flat, int n_ligands, int max_atoms, float* D,
+                                int* auto_index, double* quat, double* trans, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross attention (RowAttentionBlock / Attention._attention, models/cross_att.py:118-134,

@@ -137,6 +137,8 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp],
     "fabind_pose_relax": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f,
                           _f, _f, _f, _f, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "fabind_pose_score": [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp,
+                          _vp, _vp, _vp, _vp],
     "fabind_embed_bounds": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "fabind_embed_conformers": [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint, _i, _i, _i, _f, _f, _f, _f, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _vp],

@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libfabind_hip.so")
-SOURCES = ["capi.hip", "gemm.hip", "graph.hip", "gcl.hip", "fused_edge.hip", "fused_edge_fwd2.hip", "fused_edge_fwd3.hip", "fused_edge_bwd3.hip", "fused_edge_bwd4.hip", "pair_fused.hip", "attn.hip", "inter_attn_rows.hip", "attn_mfma.hip", "norm.hip", "bwd.hip", "post_optim.hip", "distgen.hip", "node_chain.hip", "heads.hip", "symmetry.hip", "pose_cluster.hip", "optim.hip", "ranking.hip", "conformer.hip", "conformer_fit.hip", "topology.hip", "pose_check.hip", "protein_contacts.hip", "pose_relax.hip", "embed.hip", "conformer_rmsd.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "graph.hip", "gcl.hip", "fused_edge.hip", "fused_edge_fwd2.hip", "fused_edge_fwd3.hip", "fused_edge_bwd3.hip", "fused_edge_bwd4.hip", "pair_fused.hip", "attn.hip", "inter_attn_rows.hip", "attn_mfma.hip", "norm.hip", "bwd.hip", "post_optim.hip", "distgen.hip", "node_chain.hip", "heads.hip", "symmetry.hip", "pose_cluster.hip", "optim.hip", "ranking.hip", "conformer.hip", "conformer_fit.hip", "topology.hip", "pose_check.hip", "protein_contacts.hip", "pose_relax.hip", "embed.hip", "conformer_rmsd.hip", "pose_score.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "-I" + INCLUDE, "-I" + CSRC]
 

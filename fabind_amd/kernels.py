@@ -1651,6 +1651,20 @@ def pose_protein_check(poses, atom_off, n_complex, max_atoms, plan_status, lig_r
           "fabind_pose_protein_check")
 
 
+def pose_score(poses, atom_off, n_complex, max_atoms, lig_status, lig_types, n_torsions, grid_status, origin, dims, cell_off, kept_off,
+               cell_ptr, xyz, atom_id, prot_off, prot_types, edge, cutoff, params, terms, inter, total, n_pairs, per_atom, flags):
+    """csrc/pose_score.hip: the five term sums, the weighted and the torsion-scaled energy, the pair count and the flag word of every
+    (complex, pose) of the fp32 [S, N, 3] poses into terms fp32 [B, S, 5] / inter, total fp32 [B, S] / n_pairs, flags int32 [B, S], one
+    launch.  params: fp64 [6] on the device = the five weights and the torsion weight; n_torsions=None: no torsions; per_atom=None: the
+    per-atom energies fp32 [S, N] are not written."""
+    S, N = poses.shape[0], poses.shape[1]
+    check(_lib.load().fabind_pose_score(ptr(poses), int(S), int(N), ptr(atom_off), int(n_complex), int(max_atoms), ptr(lig_status),
+                                        ptr(lig_types), ptr(n_torsions), ptr(grid_status), ptr(origin), ptr(dims), ptr(cell_off),
+                                        ptr(kept_off), ptr(cell_ptr), ptr(xyz), ptr(atom_id), ptr(prot_off), ptr(prot_types), float(edge),
+                                        float(cutoff), ptr(params), ptr(terms), ptr(inter), ptr(total), ptr(n_pairs), ptr(per_atom),
+                                        ptr(flags), stream()), "fabind_pose_score")
+
+
 def pose_relax(x0, target, angles0, atom_off, n_complex, tor_off, quad, side, t_total, max_atoms, max_torsions, plan_status, cls, lig_radii,
                grid_status, origin, dims, cell_off, kept_off, cell_ptr, prot_xyz, prot_radii, edge, max_reach, weights, max_iters, tol, coords,
                angles, energy0, energy, iters, stop, status, trace):

@@ -171,3 +171,14 @@ def valid_sampling_metrics(rmsd, cdis, conf, valid, top_n=1):
     names += ["valid_share", "top1_valid_share", "rmsd_lt2_and_valid"]
     vals += [v.double().mean(), v.gather(0, top1).double().mean(), (v.gather(0, pick) & (rmsd.gather(0, pick) < 2)).any(0).double().mean()]
     return dict(zip(names, torch.stack(vals).tolist()))
+
+
+def energy_sampling_metrics(rmsd, cdis, energy, valid=None, top_n=1):
+    """The sampling table with a physics-based energy as the ranking signal (`fabind_amd.scoring.score_poses(...).total.t()`; lower is
+    better) where no confidence model exists: `sampling_metrics` (valid=None) or `valid_sampling_metrics` called with conf = -energy.
+    A pose without an energy (NaN: NONFINITE or UNCHECKED) ranks last.  rmsd, cdis, energy (and valid): [S, B].
+    -> dict of python floats."""
+    conf = torch.where(torch.isnan(energy), torch.full_like(energy, float("-inf")), -energy)
+    if valid is None:
+        return sampling_metrics(rmsd, cdis, conf, top_n)
+    return valid_sampling_metrics(rmsd, cdis, conf, valid, top_n)

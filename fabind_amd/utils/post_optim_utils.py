@@ -175,6 +175,41 @@ def check_protein_contacts_batched(predict_compound_coords, compound_batch, plan
     return res.ok.t(), res.flags.t(), res.stats.transpose(0, 1)
 
 
+def score_compound_coords_batched(predict_compound_coords, compound_batch, lig_types, grid, prot_types, torsion_plan=None, **options):
+    """A Vina-style intermolecular energy of predicted (or fitted, or relaxed) ligand coordinates for the inference scripts:
+    `scoring.score_poses` (csrc/pose_score.hip) behind the conventions of this module.  predict: [sum Nc, 3] ([S, sum Nc, 3] for S
+    sampled poses) in the frame of the grid; compound_batch: sorted ligand id per atom; lig_types: int [sum Nc] type words
+    (`scoring.ligand_types`); grid: the `validity.protein_grid` ProteinGrid of the same complexes built with edge >= cutoff
+    (`protein_grid(edge=8.0)`); prot_types: int [M] type words of the grid's atoms (`scoring.protein_types_from_pdb`);
+    torsion_plan: the `conformer.rotatable_bonds` TorsionPlan, whose torsion counts scale the total and whose status marks ligands
+    that are not scored, or None (no torsions); options: weights, cutoff, torsion_weight, per_atom as `score_poses` takes them.
+    -> (total float32 [L] ([S, L]): lower is better, NaN where a pose is not scored, flags int32 [L] ([S, L]), the PoseScores)."""
+    from .. import scoring
+    if not predict_compound_coords.is_cuda:
+        raise RuntimeError("fabind_amd: the pose score runs on a HIP device only (no CPU fallback); got %s"
+                           % predict_compound_coords.device)
+    if grid is None:
+        raise ValueError("score_compound_coords_batched needs the ProteinGrid of the proteins (validity.protein_grid(edge=8.0))")
+    dev = predict_compound_coords.device
+    L = int(grid.prot_off.numel()) - 1
+    cb = torch.as_tensor(compound_batch).to(dev).long()
+    if cb.dim() != 1 or cb.numel() != predict_compound_coords.shape[-2]:
+        raise ValueError("compound_batch must be [%d]; got %s" % (predict_compound_coords.shape[-2], tuple(cb.shape)))
+    if cb.numel() and (int(cb.min()) < 0 or int(cb.max()) >= L or bool((cb[1:] < cb[:-1]).any())):
+        raise ValueError("compound_batch is not sorted or names a ligand outside the complexes of `grid`")
+    atom_off = torch.zeros(L + 1, dtype=torch.int32, device=dev)
+    atom_off[1:] = torch.bincount(cb, minlength=L).cumsum(0).to(torch.int32)
+    n_torsions = status = None
+    if torsion_plan is not None:
+        if not torch.equal(torsion_plan.atom_off.to(dev), atom_off):
+            raise ValueError("compound_batch does not match the ligands of `torsion_plan`")
+        n_torsions, status = torch.diff(torsion_plan.off), torsion_plan.status
+    res = scoring.score_poses(predict_compound_coords, atom_off, lig_types, grid, prot_types, n_torsions=n_torsions, status=status, **options)
+    if predict_compound_coords.dim() == 2:
+        return res.total[:, 0], res.flags[:, 0], res
+    return res.total.t(), res.flags.t(), res
+
+
 def post_optimize_compound_coords(reference_compound_coords, predict_compound_coords, total_epoch=1000, LAS_edge_index=None,
                                   mode=0):
     """The reference's per-ligand entry point: -> (x [Nc, 3], loss of the last epoch (float), RMSD (float)).  `mode` only

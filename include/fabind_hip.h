@@ -86,6 +86,7 @@ const char* fabind_last_error(void);
  *     Likewise fabind_pose_relax (csrc/pose_relax.hip: poses relaxed out of protein and internal clashes in torsion space).
  *     Likewise fabind_embed_bounds / fabind_embed_conformers (csrc/embed.hip: start conformers from the bond list by distance geometry).
  *     Likewise fabind_conformer_pair_rmsd / fabind_conformer_cross_rmsd (csrc/conformer_rmsd.hip: superposed symmetric RMSD of conformers).
+ *     Likewise fabind_pose_score (csrc/pose_score.hip: a Vina-style intermolecular energy of sampled poses).
  * A binding must refuse a library whose version differs from the header it was written against. */
 #define FABIND_ABI_VERSION 19
 int fabind_abi_version(void);
@@ -722,6 +723,22 @@ int fabind_conformer_pair_rmsd(const float* X, int n_conf, int n_atoms, const in
 int fabind_conformer_cross_rmsd(const float* X, int n_conf, const float* Y, int n_ref, int n_atoms, const int* atom_off,
                                 const int* flat_off, const int* auto_cnt, const int* flat, int n_ligands, int max_atoms, float* D,
                                 int* auto_index, double* quat, double* trans, hipStream_t stream);
+/* fabind_pose_score (csrc/pose_score.hip; a backward-compatible addition under ABI 19; fabind_amd/scoring.py documents every layout and
+ * DESIGN.md section 22 every rule): the Vina-style intermolecular energy of poses fp32 [n_pose, n_atoms, 3] of the ligands atom_off int32
+ * [n_complex + 1] against the kept atoms of the complex's cell list (fabind_protein_grid, built with edge >= cutoff), one launch, one
+ * wave per (complex, pose).  lig_types int32 [n_atoms] and prot_types int32 [sum protein atoms] (read at prot_off[b] + atom_id) are
+ * type words: radius class in bits 0-3 (C, N, O, P, S, F, Cl, Br, I, metal), 16 hydrophobic, 32 donor, 64 acceptor.  n_torsions int32
+ * [n_complex] or NULL (0); params fp64 [6] on the device = the five weights and the torsion weight.  Pairs with r^2 < cutoff^2 in
+ * float64; d = r - R_i - R_j.  terms fp32 [n_complex, n_pose, 5] = the unweighted sums (gauss1, gauss2, repulsion, hydrophobic, hbond),
+ * inter = sum_k w_k term_k, total = inter / (1 + params[5] n_torsions) fp32 [n_complex, n_pose], n_pairs int32 [n_complex, n_pose],
+ * per_atom fp32 [n_pose, n_atoms] or NULL: the weighted energy of every ligand atom, flags int32 [n_complex, n_pose]: 128 NONFINITE (a
+ * NaN or infinite coordinate: every number of the pose NaN), 256 UNCHECKED (lig_status or grid_status != 0: NaN, no pairs).  Fixed
+ * summation order, no atomics: an entry is the same bits alone, in any batch, among any n_pose and on a repeat. */
+int fabind_pose_score(const float* poses, int n_pose, int n_atoms, const int* atom_off, int n_complex, int max_atoms,
+                      const int* lig_status, const int* lig_types, const int* n_torsions, const int* grid_status, const int* origin,
+                      const int* dims, const int* cell_off, const int* kept_off, const int* cell_ptr, const float* xyz,
+                      const int* atom_id, const int* prot_off, const int* prot_types, float edge, float cutoff, const double* params,
+                      float* terms, float* inter, float* total, int* n_pairs, float* per_atom, int* flags, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Cross attention (RowAttentionBlock / Attention._attention, models/cross_att.py:118-134,
